@@ -12,9 +12,14 @@ defined as a global batch of 16 / 8 clouds data-parallel over 8 GPUs -- are sele
                                                                  # statistics over the global batch (= one process on 16)
     python bench.py --config C5                                  # the whole configuration on one GPU
 
-One JSON line on rank 0 (contract in the task statement) carrying `roofline` (the sparse operator
-apply, measured live with HIP events) and `cpu_baseline` (the oracle = CPU port of the reference
-path, timed on this box's host cores on a bounded sample).
+One JSON line on rank 0: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the configuration.  A
+plain run only sets up, warms up, times the `--steps` steps and prints that line.  `--full` adds everything else the
+benchmark measures: `roofline` (the sparse operator apply, measured live with HIP events, and the same kernels inside the
+replayed step), `exact_chain_ms_per_step` (the step on the exact fp32 MFMA chain) and `cpu_baseline` (the oracle = CPU port
+of the reference path, timed on the host cores on a bounded sample).
+
+    python bench.py --full                                       # the line with every measurement beside the headline
+    python bench.py --dump-outputs DIR                           # + what the last timed step computed, DIR/<name>.npy
 """
 import argparse
 import json
@@ -46,6 +51,12 @@ def parse(argv=None):
     ap.add_argument("--batch", type=int, default=None, help="clouds per GPU (weak scaling; default: the configuration's batch)")
     ap.add_argument("--points", type=int, default=None, help="points per cloud (default: the configuration's)")
     ap.add_argument("--k", type=int, default=None, help="neighbours (default: the configuration's)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the roofline of the operator applies, the step on the exact fp32 chain, the "
+                         "in-step stamps and the CPU baseline (each switched off again by its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, logits, parameter gradients, updated "
+                         "parameters and BatchNorm statistics) as DIR/<name>.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-exact-chain", action="store_true",
                     help="skip the second timing of the same step with every dense product on the exact fp32 MFMA chain")
@@ -477,6 +488,35 @@ def cpu_baseline(args):
                        f"host: {phys} physical cores / {hw} hardware threads")
 
 
+DUMP_BYTES = 64 << 20
+
+
+def step_outputs(model, loss, out):
+    """What a caller of the timed step receives after its last step: the loss, the logits, every parameter gradient,
+    the parameters after the update and the BatchNorm running statistics (the last three flat, in named_parameters /
+    named_buffers order) -> {name: float32 numpy array}."""
+    params = list(model.parameters())
+    with torch.no_grad():
+        flat = lambda ts: torch.cat([t.detach().reshape(-1).float() for t in ts]).cpu().numpy()
+        return {"loss": loss.detach().float().cpu().numpy(), "logits": out.detach().float().cpu().numpy(),
+                "grads": flat([p.grad for p in params if p.grad is not None]), "params": flat(params),
+                "bn_stats": flat([b for b in model.buffers() if b.is_floating_point()])}
+
+
+def dump_outputs(directory, arrays, limit=DUMP_BYTES):
+    """DIR/<name>.npy for every array; above `limit` bytes in all, every array keeps the same share of its elements as a
+    fixed, seeded sample (flattened, in index order)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > limit:
+            keep = max(1, a.size * limit // total)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def self_launch_command(args, argv, port=None):
     """The command line `python bench.py --gpus N` re-executes itself as when no launcher set WORLD_SIZE: the driver's own
     multi-GPU form, one rank per GPU of this node over RCCL (rendezvous on 127.0.0.1: the container hostname may not
@@ -532,6 +572,7 @@ def main(argv=None):
                for i in range(max(1, args.resident_batches))]
     data = batches[0]
     counter = [0]
+    eager_out = [None]
 
     def next_batch():
         counter[0] += 1
@@ -540,13 +581,14 @@ def main(argv=None):
     def eager_step():
         b = next_batch()
         ddp.zero_grad()
-        loss = calc_loss(ddp(b), b.y)
+        eager_out[0] = ddp(b)
+        loss = calc_loss(eager_out[0], b.y)
         loss.backward()
         ddp.reduce_gradients()
         opt.step()
         return loss
 
-    step, launch = eager_step, "eager launches"
+    step, launch, last_out = eager_step, "eager launches", lambda: eager_out[0]
     if not args.no_graph:
         # forward + loss + backward (+ SGD update when there is no all-reduce in between) replayed from
         # one captured HIP graph; same kernels, same work per step, one host call.
@@ -564,6 +606,7 @@ def main(argv=None):
 
             def step():
                 return gstep(next_batch())
+            last_out = lambda: gstep.out
             launch = ("HIP-graph replay" if not use_dist else
                       "one HIP graph with the BatchNorm-statistics and gradient all-reduces captured" if gstep.capture_collectives
                       else "HIP-graph replay x2 around the gradient all-reduce")
@@ -590,10 +633,13 @@ def main(argv=None):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax)
     assert torch.isfinite(loss).item(), "loss is not finite"
+    if args.dump_outputs and rank == 0:          # before anything below runs further steps on the same model
+        dump_outputs(args.dump_outputs, step_outputs(model, loss, last_out()))
     # The same step with every dense product on the exact fp32 MFMA chain (option 3; bitwise an fmaf chain): the number the
     # fp32-equivalence claim of the split products travels with.  Not `value`: reported beside it.
     exact_ms = None
-    if world == 1 and not use_dist and not args.no_exact_chain and os.environ.get("DC_GEMM_EXACT", "0") in ("", "0"):
+    if (args.full and world == 1 and not use_dist and not args.no_exact_chain
+            and os.environ.get("DC_GEMM_EXACT", "0") in ("", "0")):
         from deltaconv_amd._lib import lib as _lib
         _lib.raw("dc_set_option")(3, 1)
         try:
@@ -615,14 +661,16 @@ def main(argv=None):
         finally:
             _lib.raw("dc_set_option")(3, 0)
     stamped = None
-    if rank == 0 and world == 1 and not use_dist and not args.no_graph and not args.no_in_step_stamps:
+    if args.full and rank == 0 and world == 1 and not use_dist and not args.no_graph and not args.no_in_step_stamps:
         try:
             stamped = in_step_stamps(model, calc_loss, static, opt, args.batch * args.points, args.k)
         except Exception as e:
             print(f"[bench] in-step stamps failed: {e!r}", file=sys.stderr)
     if rank == 0:
-        graph, grad, div = model.deltanet_base.build_operators(data)
-        roof = apply_roofline(graph, grad, div, cfg["C"])
+        roof = None
+        if args.full:
+            graph, grad, div = model.deltanet_base.build_operators(data)
+            roof = apply_roofline(graph, grad, div, cfg["C"])
         graded = [r for r in (stamped or {}).get("div_curl_norm", []) if r["C"] == cfg["C"]]
         if graded:
             # THE graded number: the kernel as it runs inside the replayed training step (its real predecessors, its real
@@ -661,11 +709,11 @@ def main(argv=None):
                                    + ("BatchNorm statistics over the global batch, " if (args.sync_bn and use_dist) else "")
                                    + launch,
                        "name": args.config, "global_batch": args.batch * world, "parallelism": f"dp{world}"},
-            "roofline": roof,
-            "exact_chain_ms_per_step": exact_ms,
         }
-        if not args.no_cpu_baseline and world == 1:      # the CPU leg is timed at N=1 only (rank 0)
-            out["cpu_baseline"] = cpu_baseline(args)
+        if args.full:
+            out.update(roofline=roof, exact_chain_ms_per_step=exact_ms)
+            if not args.no_cpu_baseline and world == 1:      # the CPU leg is timed at N=1 only (rank 0)
+                out["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(out))
     if use_dist:
         dist.barrier()

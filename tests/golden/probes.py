@@ -1,4 +1,6 @@
 """Seeded probe vectors / gradient summaries shared by the golden generator and the tests."""
+import math
+
 import numpy as np
 import torch
 
@@ -22,4 +24,6 @@ def param_summaries(model):
 
 
 def state_checksum(model):
-    return np.array([float(t.double().abs().sum()) for t in model.state_dict().values()])
+    """Sum of |entries| per state tensor, correctly rounded (math.fsum): the same weights give the same bits on every
+    host, whatever order torch's vectorised, threaded reduction would add them in."""
+    return np.array([math.fsum(t.detach().double().abs().reshape(-1).tolist()) for t in model.state_dict().values()])

@@ -65,3 +65,25 @@ def test_config_and_strong_scaling_flags():
     assert bench.per_rank_clouds(bench.parse(["--config", "C3", "--batch", "4"]), 2) == 4
     for name, cfg in CONFIGS.items():        # the table is BASELINE.json's: sizes of SURVEY.md section 8
         assert cfg["B"] * cfg["N"] in (32768, 65536) and cfg["k"] in (20, 30)
+
+
+def test_full_and_dump_flags():
+    """A plain run is lean: everything beside the headline sits behind `--full`; `--dump-outputs DIR` is off by default."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert (a.full, a.dump_outputs) == (True, "out")
+
+
+def test_dump_outputs_caps_the_total_with_a_fixed_sample(tmp_path):
+    import numpy as np
+    arrays = {"big": np.arange(4000, dtype=np.float32), "small": np.ones((10, 10), dtype=np.float32)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    assert (np.load(tmp_path / "all" / "big.npy") == arrays["big"]).all()
+    assert np.load(tmp_path / "all" / "small.npy").shape == (10, 10)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays, limit=4100)
+    big = [np.load(tmp_path / run / "big.npy") for run in ("a", "b")]
+    small = np.load(tmp_path / "a" / "small.npy")
+    assert (big[0] == big[1]).all() and big[0].dtype == np.float32
+    assert big[0].nbytes + small.nbytes <= 4100 and (np.diff(big[0]) > 0).all()

@@ -13,11 +13,11 @@ from tests.helpers import ROOT
 pytestmark = pytest.mark.gpu
 
 
-def test_bench_under_torchrun_single_rank():
+def test_bench_under_torchrun_single_rank(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
-           "--warmup", "2", "--no-cpu-baseline", "--force-dist"]
+           "--warmup", "2", "--full", "--no-cpu-baseline", "--force-dist", "--dump-outputs", str(tmp_path)]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -27,6 +27,9 @@ def test_bench_under_torchrun_single_rank():
         assert key in d
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["value"] > 0 and d["scaling"] == "weak" and d["dtype"] == "f32"
     assert d["roofline"]["bound"] == "hbm" and 0 < d["roofline"]["frac"] < 1
+    import numpy as np
+    dumped = {n: np.load(tmp_path / f"{n}.npy") for n in ("loss", "logits", "grads", "params", "bn_stats")}
+    assert dumped["logits"].shape == (32, 40) and all(a.dtype == np.float32 and np.isfinite(a).all() for a in dumped.values())
 
 
 def test_graph_replay_with_gradient_reducer_and_sync_bn():

@@ -476,18 +476,22 @@ def test_c1_train_b1_raises_like_reference():
 
 def test_c1_backbone_train_b1():
     """C1 (ii): forward + backward through DeltaNetBase + lin_embedding at B = 1 (train-mode BatchNorm over the
-    1024 rows is well defined) vs the oracle."""
+    1024 rows is well defined) vs the oracle in fp64.  The oracle's own fp32 run is no yardstick here: it sits 1.4e-2 to
+    2.3e-2 of a parameter's gradient scale off fp64 (lin_embedding's BatchNorm, layer-3 max-aggregation), which one
+    depending on torch's CPU thread count; the HIP path is within 1e-3."""
     b = synthetic_batch(1, 1024, seed=82)
-    ref, model = _oracle_pair("cls", dict(in_channels=3, num_classes=40), 20)
+    ref32, model = _oracle_pair("cls", dict(in_channels=3, num_classes=40), 20)
+    ref = oracle.models.DeltaNetClassification(num_neighbors=20, in_channels=3, num_classes=40).double()
+    ref.load_state_dict(ref32.state_dict())
     ref.train(); model.train()
 
     def run(m, data):
         xs = m.deltanet_base(data)
         e = m.lin_embedding(torch.cat(list(xs), dim=1))
-        w = probe_vec(tuple(e.shape), 31).float().to(e.device)
+        w = probe_vec(tuple(e.shape), 31).to(e.dtype).to(e.device)
         (e * w).sum().backward()
         return e
-    eo = run(ref, b)
+    eo = run(ref, Batch(b.pos.double(), b.batch, b.norm.double(), None, b.y))
     ed = run(model, b.to(DEV))
     assert rel_err(ed, eo) < 1e-3
     gmax = max(float(p.grad.abs().max()) for p in ref.parameters() if p.grad is not None)

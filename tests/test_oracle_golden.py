@@ -1,5 +1,7 @@
 """Pin the CPU oracle against outputs of the REAL reference (tests/golden/*.npz, produced by
 tests/golden/make_golden.py from /root/reference).  CPU-only; no HIP involved."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -161,13 +163,17 @@ def build_oracle_model(kind, kw, k, lam, dt):
 @pytest.mark.parametrize("tag", ["f32", "f64"])
 def test_model_step(name, tag):
     """Whole-model train-mode step (dropout off): same seed => same init as the reference
-    (checked by checksum), then logits / loss / gradient summaries / BN running stats."""
+    (checked bit for bit by the correctly rounded checksum of tests/golden/make_golden_checksums.py), then logits /
+    loss / gradient summaries / BN running stats."""
+    import json
     from tests.golden.probes import param_summaries, state_checksum
+    from tests.helpers import GOLDEN
     kind, kw, normals = MODELS[name]
     g = load_golden(name)
     dt = torch.float32 if tag == "f32" else torch.float64
     model = build_oracle_model(kind, kw, g["k"], g["lam"], dt)
-    assert np.allclose(state_checksum(model), g["state_checksum"].numpy(), rtol=0, atol=0)
+    want = json.load(open(os.path.join(GOLDEN, "state_checksums.json")))[name]
+    assert np.allclose(state_checksum(model), np.array(want), rtol=0, atol=0)
     model = model.to(dt).train()
     for m in model.modules():
         if isinstance(m, torch.nn.Dropout):

@@ -4,7 +4,7 @@ TAG=$1; A=$2; B=$3; shift 3
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 for round in 1 2; do
 for spec in "$A" "$B"; do
-  env $spec python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-exact-chain "$@" > $OUT/bench_${spec//[^A-Za-z0-9]/_}_$round.log 2>&1
+  env $spec python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-exact-chain "$@" > $OUT/bench_${spec//[^A-Za-z0-9]/_}_$round.log 2>&1
   tail -1 $OUT/bench_${spec//[^A-Za-z0-9]/_}_$round.log | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']

@@ -8,7 +8,7 @@ for lib in "$@"; do
   if [ "$lib" = default ]; then unset DELTACONV_HIP_LIB; else export DELTACONV_HIP_LIB=$PWD/$lib; fi
   echo "=== round $round lib: $lib"
   [ $round = 1 ] && python tools/instep_gap_lab.py 2>&1 | grep -E "^A|^B|^C"
-  python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-exact-chain 2>/dev/null | tail -1 | python -c "
+  python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-exact-chain 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']
 print('  bench ms', round(d['ms_per_step'],4), 'graded exec', (r.get('execution_only') or {}).get('us'))

@@ -8,7 +8,7 @@ ulimit -c 0
 timeout 1500 python -m pytest tests -q -m gpu --tb=short -p no:cacheprovider -rA 2>&1 | grep -v "^PASSED" > $OUT/pytest_gpu.log
 grep -E "passed|failed|pinned slots|scale 2\^" $OUT/pytest_gpu.log | tail -12
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log
-timeout 500 python bench.py --steps 20 --warmup 5 ${BENCH_FLAGS:-} > $OUT/bench.log 2>&1; tail -1 $OUT/bench.log > $OUT/bench.json
+timeout 500 python bench.py --full --steps 20 --warmup 5 ${BENCH_FLAGS:-} > $OUT/bench.log 2>&1; tail -1 $OUT/bench.log > $OUT/bench.json
 python - <<PY
 import json
 d = json.load(open("$OUT/bench.json"))

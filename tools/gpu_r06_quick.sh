@@ -8,7 +8,7 @@ export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 ulimit -c 0
 timeout 900 python -m pytest tests -q -m gpu --tb=short -p no:cacheprovider -k "$KEXPR" 2>&1 | tail -25 > $OUT/pytest_quick.log
 tail -5 $OUT/pytest_quick.log
-timeout 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench.log 2>&1; tail -1 $OUT/bench.log > $OUT/bench.json
+timeout 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench.log 2>&1; tail -1 $OUT/bench.log > $OUT/bench.json
 python - <<PY
 import json
 d = json.load(open("$OUT/bench.json"))
@@ -20,7 +20,7 @@ for name, rows in (r.get("in_step_kernels") or {}).items():
 PY
 for spec in "C4 2" "C4 16" "C5 1" "C5 8" "C3 32"; do
   set -- $spec
-  timeout 300 python bench.py --config $1 --global-batch $2 --steps 20 --warmup 5 --no-cpu-baseline --no-exact-chain > $OUT/bench_$1_$2.log 2>&1
+  timeout 300 python bench.py --full --config $1 --global-batch $2 --steps 20 --warmup 5 --no-cpu-baseline --no-exact-chain > $OUT/bench_$1_$2.log 2>&1
   tail -1 $OUT/bench_$1_$2.log | python -c "
 import json,sys
 try:
