@@ -53,7 +53,9 @@ static thread_local DcFinPending g_fin[DC_FIN_MAX];
 static thread_local int g_fin_count = 0;
 static thread_local bool g_fin_open = false, g_fin_request = false, g_gemm_request = false;
 bool dc_gemm_take_request() {
-    const bool take = g_fin_open && g_gemm_request && g_fin_request;   // (a queued product needs its finaliser queued behind it)
+    // a queued product needs its finaliser queued behind it: with the finaliser queue full, that finaliser would launch at once,
+    // ahead of the product that writes its partials
+    const bool take = g_fin_open && g_gemm_request && g_fin_request && g_fin_count < DC_FIN_MAX;
     g_gemm_request = false;
     return take;
 }

@@ -926,8 +926,12 @@ void gemm_single_thunk(const GemmP& p, unsigned blocks, size_t lds, hipStream_t 
 template <int BM, int BN, int AL, int BL, int MODE, int EPI, int PRO, int X3, int BP>
 void gemm_pair_thunk(const GemmP& p0, const GemmP& p1, unsigned b0, unsigned b1, size_t lds, hipStream_t s) {
     static unsigned long long configured = 0;
-    if (!dc_ensure_lds(&configured, reinterpret_cast<const void*>(&gemm_pair_kernel<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP>), lds, "dense product pair"))
+    if (!dc_ensure_lds(&configured, reinterpret_cast<const void*>(&gemm_pair_kernel<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP>), lds, "dense product pair")) {
+        (void)dc_take_lds_failure();        // the single kernel's opt-in held when both were queued: one launch each instead
+        gemm_single_thunk<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP>(p0, b0, lds, s);
+        gemm_single_thunk<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP>(p1, b1, lds, s);
         return;
+    }
     GemmP q1 = p1;
     q1.stagger = 0;                         // (the phase shift is a first-round device: the second product's workgroups come later)
     hipLaunchKernelGGL((gemm_pair_kernel<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP>), dim3(b0 + b1, 1), dim3(NT), lds, s, p0, q1, b0);

@@ -72,11 +72,11 @@ DC_EXPORT int dc_sgd_step(const int64_t* params, const int64_t* grads, const int
                           const float* lr, float momentum, float weight_decay, void* stream) {
     DC_REQUIRE(count >= 0 && (count == 0 || (params && grads && bufs && numel && lr)), "dc_sgd_step: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    for (int t0 = 0; t0 < count; t0 += SGD_MAX_TENSORS) {
+    for (int t0 = 0; t0 < count;) {
         SgdTable t;
         t.count = 0;
-        int chunks = 0;
-        for (int i = t0; i < count && t.count < SGD_MAX_TENSORS; ++i) {
+        int chunks = 0, i = t0;
+        for (; i < count && t.count < SGD_MAX_TENSORS; ++i) {
             DC_REQUIRE(numel[i] >= 0 && numel[i] < 2147483647L, "dc_sgd_step: tensor too large");
             if (numel[i] == 0) continue;
             DC_REQUIRE(params[i] && grads[i] && bufs[i], "dc_sgd_step: null tensor");
@@ -88,6 +88,7 @@ DC_EXPORT int dc_sgd_step(const int64_t* params, const int64_t* grads, const int
             t.first_chunk[c] = chunks;
             chunks += dc_cdiv(numel[i], SGD_CHUNK);
         }
+        t0 = i;                         // the next window starts behind the last entry this one looked at (empty ones included)
         t.first_chunk[t.count] = chunks;
         if (chunks) hipLaunchKernelGGL(sgd_kernel, dim3(chunks), dim3(SGD_THREADS), 0, s, t, lr, momentum, weight_decay);
     }

@@ -12,8 +12,14 @@ Semantics kept per replay: kNN / MLS operators are rebuilt from the current `pos
 statistics and `num_batches_tracked` advance, Dropout draws a fresh mask (torch's graph-safe Philox
 offsets), gradients land in the same `.grad` tensors every time (do NOT call zero_grad(set_to_none)
 between replays -- the captured backward overwrites them).  The gradient all-reduce (RCCL) stays
-outside the graph; the optimizer update is captured only when `optimizer` is given (single-rank case,
-constant hyper-parameters: a learning-rate change needs `recapture()`).
+outside the graph; the optimizer update is captured only when `optimizer` is given.  A deltaconv_amd.optim
+optimizer reads its learning rates from device scalars: every call writes the groups' current values there
+(`optimizer.sync_lr()`, outside the graph), so a scheduler step between calls takes effect; other
+hyper-parameters, and the learning rate of other optimizers, are those of the capture.  The captured update
+also reads the optimizer's state tensors (momentum buffers, Adam's counters and moments, the learning-rate
+scalars) at their capture-time addresses: when the optimizer holds other tensors than the captured ones (a
+`load_state_dict` after the capture), a call raises RuntimeError instead of replaying on the old state --
+`recapture()` (whose warm-up steps are real updates) or a new GraphedTrainStep picks up the new state.
 
 ROCm note (measured on ROCm 7.2 / MI355X, tools/graph_bisect*.py history in DESIGN.md): with the
 runtime's AQL-packet capture (`DEBUG_CLR_GRAPH_PACKET_CAPTURE`, default on) a replay that follows a
@@ -28,6 +34,22 @@ from . import _ops
 from .nn.fused import invalidate_eval_coeffs, planes_snapshot
 
 _FLAG = "DEBUG_CLR_GRAPH_PACKET_CAPTURE"
+
+
+def _optimizer_tensors(optimizer):
+    """What a captured update reads besides parameters and gradients: the state tensors of every parameter, in a fixed
+    order, and the device learning-rate scalars by group (deltaconv_amd.optim)."""
+    if optimizer is None:
+        return [], {}
+    state = optimizer.state
+    out = [v for g in optimizer.param_groups for p in g["params"] for v in state.get(p, {}).values() if torch.is_tensor(v)]
+    return out, {i: hit[0] for i, hit in getattr(optimizer, "_lr_dev", {}).items()}
+
+
+def _same_tensors(now, then):
+    """(sync_lr may add scalars for groups the graph never stepped: only the captured ones must stay)"""
+    return (len(now[0]) == len(then[0]) and all(a is b for a, b in zip(now[0], then[0]))
+            and all(now[1].get(i) is t for i, t in then[1].items()))
 
 
 class GraphedTrainStep:
@@ -90,6 +112,7 @@ class GraphedTrainStep:
             self._planes_keepalive = planes_snapshot()      # raw addresses inside the graph (advisor, round 4)
             invalidate_eval_coeffs()
             self.grads = [(p, p.grad) for p in self.params if p.grad is not None]
+            self._opt_tensors = _optimizer_tensors(self.optimizer)
             return
         # with a process group alive its watchdog thread may query an event of the last warm-up all-reduce while this thread
         # captures: a global-mode capture would be invalidated by that call (seen with the captured collectives above)
@@ -112,6 +135,8 @@ class GraphedTrainStep:
         self._planes_keepalive = planes_snapshot()
         invalidate_eval_coeffs()
         self.grads = [(p, p.grad) for p in self.params if p.grad is not None]   # rewritten by every replay
+        # the optimizer state the graph reads (by address): held here, compared before every replay
+        self._opt_tensors = _optimizer_tensors(self.optimizer)
 
     def _zero(self):
         for p in self.params:
@@ -163,6 +188,14 @@ class GraphedTrainStep:
             raise RuntimeError("GraphedTrainStep: the gradient reducer re-allocated its flat buffer after capture (an eager "
                                "reduce_gradients() with a different set of live parameters); the captured graphs still use "
                                "the old one -- build a new GraphedTrainStep")
+        if self.optimizer is not None:
+            sync = getattr(self.optimizer, "sync_lr", None)
+            if sync is not None:
+                sync()                          # the scheduler's learning rate into the device scalars the graph reads
+            if not _same_tensors(_optimizer_tensors(self.optimizer), self._opt_tensors):
+                raise RuntimeError("GraphedTrainStep: the optimizer holds other state tensors than at capture (load_state_dict "
+                                   "after the capture?); the captured update would read the old ones -- call recapture() "
+                                   "(its warm-up steps are real updates) or build a new GraphedTrainStep")
         self.graph.replay()
         if self.graph_update is not None:
             self.reducer.all_reduce()           # the one collective of the step, between the two replays

@@ -11,7 +11,12 @@ sparse parameters) goes through torch's own ``step``.
 ``Adam`` is ``torch.optim.Adam`` (the optimizer of experiments/train_shapeseg.py:82) on ``dc_adam_step`` in the same way: one
 launch for all parameters, ``state[p]["step"]`` ONE device scalar shared by the parameters of a group (torch's capturable
 layout; ``state_dict`` keys and values as torch's), learning rate from a device scalar.  amsgrad / maximize groups go through
-torch's own (capturable) ``step``.
+torch's own (capturable) ``step``, and so does a group whose parameters stand at different step counts: one that gets its first
+gradient after the group's first step, or one that sits a step out without a gradient (torch counts per parameter).
+
+The learning-rate scalars are made once per group (by position) and afterwards only rewritten in place, load_state_dict
+included: a captured update keeps reading them.  Momentum buffers and Adam's moments and counters are new tensors after a
+load_state_dict; GraphedTrainStep refuses to replay a capture over them.
 """
 import ctypes
 
@@ -24,34 +29,16 @@ class SGD(torch.optim.SGD):
     def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, **kw):
         kw.pop("fused", None)           # this IS the fused form; torch's flag would only select its multi-tensor kernel
         super().__init__(params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, **kw)
-        self._lr_dev = {}               # id(group) -> [device scalar, the value it holds]
+        self._lr_dev = {}               # group index -> [device scalar, the value it holds] (_lr_scalar)
 
     def _own_kernel(self, group):
         return (group["dampening"] == 0 and not group["nesterov"] and not group.get("maximize", False)
                 and all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in group["params"]))
 
-    def _lr_scalar(self, group, device):
-        lr = float(group["lr"])
-        hit = self._lr_dev.get(id(group))
-        if hit is None or hit[0].device != device:
-            if torch.cuda.is_current_stream_capturing():      # a captured fill would rewrite the scalar in every replay
-                raise RuntimeError("SGD.step(): first step inside a graph capture -- run one eager step (or sync_lr()) before capturing")
-            hit = [torch.full((), lr, dtype=torch.float32, device=device), lr]
-            self._lr_dev[id(group)] = hit
-        elif hit[1] != lr:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("SGD.step(): the learning rate changed inside a graph capture")
-            hit[0].fill_(lr)            # a scheduler moved it: one tiny launch, outside any captured graph
-            hit[1] = lr
-        return hit[0]
-
     def sync_lr(self):
-        """Write the groups' current learning rates to their device scalars (call after scheduler.step() when the
-        optimizer step itself only runs inside graph replays)."""
-        for group in self.param_groups:
-            ps = [p for p in group["params"] if p.is_cuda]
-            if ps:
-                self._lr_scalar(group, ps[0].device)
+        """Write the groups' current learning rates to their device scalars (GraphedTrainStep does this before every replay;
+        call it after scheduler.step() when the optimizer step itself runs inside graph replays of your own)."""
+        _sync_lr(self._lr_dev, self.param_groups, "SGD")
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -60,7 +47,7 @@ class SGD(torch.optim.SGD):
             with torch.enable_grad():
                 loss = closure()
         leftover = False
-        for group in self.param_groups:
+        for gi, group in enumerate(self.param_groups):
             if not self._own_kernel(group):
                 leftover = True
                 continue
@@ -76,7 +63,7 @@ class SGD(torch.optim.SGD):
             grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in ps]
             n = len(ps)
             arr = lambda vals: (ctypes.c_int64 * n)(*vals)
-            lr = self._lr_scalar(group, ps[0].device)
+            lr = _lr_scalar(self._lr_dev, gi, group, ps[0].device, "SGD")
             rc = lib.raw("dc_sgd_step")(arr(p.data_ptr() for p in ps), arr(g.data_ptr() for g in grads),
                                         arr(b.data_ptr() for b in bufs), arr(p.numel() for p in ps), n, lr.data_ptr(),
                                         float(group["momentum"]), float(group["weight_decay"]),
@@ -93,20 +80,31 @@ class SGD(torch.optim.SGD):
         return loss
 
 
-def _lr_scalar(cache, group, device, who):
+def _lr_scalar(cache, index, group, device, who):
+    """The device scalar the kernel of group `index` reads its learning rate from.  Made once, outside any capture; afterwards
+    only rewritten in place (a captured update keeps reading the same address across scheduler steps and load_state_dict)."""
     lr = float(group["lr"])
-    hit = cache.get(id(group))
+    hit = cache.get(index)
     if hit is None or hit[0].device != device:
-        if torch.cuda.is_current_stream_capturing():
+        if torch.cuda.is_current_stream_capturing():      # a captured fill would rewrite the scalar in every replay
             raise RuntimeError(f"{who}.step(): first step inside a graph capture -- run one eager step (or sync_lr()) before capturing")
         hit = [torch.full((), lr, dtype=torch.float32, device=device), lr]
-        cache[id(group)] = hit
+        cache[index] = hit
     elif hit[1] != lr:
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError(f"{who}.step(): the learning rate changed inside a graph capture")
-        hit[0].fill_(lr)
+        hit[0].fill_(lr)            # a scheduler moved it: one tiny launch, outside any captured graph
         hit[1] = lr
     return hit[0]
+
+
+def _sync_lr(cache, groups, who):
+    for i, group in enumerate(groups):
+        p = next((p for p in group["params"] if p.is_cuda), None)
+        if p is not None and not isinstance(group["lr"], torch.Tensor):
+            _lr_scalar(cache, i, group, p.device, who)
+    for i in [i for i in cache if i >= len(groups)]:     # (groups that no longer exist)
+        del cache[i]
 
 
 class Adam(torch.optim.Adam):
@@ -114,9 +112,9 @@ class Adam(torch.optim.Adam):
         kw.pop("fused", None)
         self._capturable_arg = kw.pop("capturable", None)
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, **kw)
-        self._lr_dev = {}
+        self._lr_dev = {}               # group index -> [device scalar, the value it holds] (_lr_scalar)
         self._ticket = {}               # device -> int32 zero (the kernel's "last workgroup" counter)
-        self._masters = {}              # id(group) -> the step counter its parameters share
+        self._masters = {}              # group index -> the step counter its parameters share
 
     def add_param_group(self, param_group):
         """Groups of device parameters keep their step counters on the device (torch's `capturable` layout: its own step, where
@@ -138,10 +136,7 @@ class Adam(torch.optim.Adam):
                 and all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in group["params"]))
 
     def sync_lr(self):
-        for group in self.param_groups:
-            ps = [p for p in group["params"] if p.is_cuda]
-            if ps and not isinstance(group["lr"], torch.Tensor):
-                _lr_scalar(self._lr_dev, group, ps[0].device, "Adam")
+        _sync_lr(self._lr_dev, self.param_groups, "Adam")
 
     def state_dict(self):
         """torch's layout with one INDEPENDENT step tensor per parameter: a plain torch.optim.Adam that loads the shared
@@ -151,16 +146,25 @@ class Adam(torch.optim.Adam):
                        for k, v in sd["state"].items()}
         return sd
 
-    def _shared_step(self, group, ps):
+    def _shared_step(self, gi, group, ps):
         """The ONE device step counter of the group: created with the first state, re-shared after a load_state_dict
-        (which hands every parameter its own copy -- equal values, checked once, outside any capture)."""
-        live = [self.state[p] for p in group["params"] if "step" in self.state[p]]
-        master = self._masters.get(id(group))
-        if master is not None and all(st["step"] is master for st in live):
+        (which hands every parameter its own copy -- equal values, checked once, outside any capture).  None: torch's
+        per-parameter step -- counters at different values, or a set of stepped parameters that differs from the set with
+        state (a parameter that joins late starts at step 0, one that sits a step out keeps its count, as in torch)."""
+        live = [st for st in (self.state.get(p, {}) for p in group["params"]) if "step" in st]    # (.get: no empty entries)
+        mine = [self.state.get(p, {}).get("step") for p in ps]
+        master = self._masters.get(gi)
+        if master is not None and len(live) == len(ps) and all(t is master for t in mine):
             return master
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("Adam.step(): optimizer state is created / re-shared inside a graph capture -- run one eager step first")
         dev = ps[0].device
+        if live and (len(live) != len(ps) or any(t is None for t in mine)):
+            if len({id(st["step"]) for st in live}) < len(live):
+                for st in live:                 # torch's step advances every counter it is handed: one tensor each
+                    st["step"] = st["step"].clone()
+            self._masters.pop(gi, None)
+            return None
         if not live:
             master = torch.zeros((), dtype=torch.float32, device=dev)
         else:
@@ -170,7 +174,7 @@ class Adam(torch.optim.Adam):
             master = vals[0].clone()
         for st in live:
             st["step"] = master
-        self._masters[id(group)] = master
+        self._masters[gi] = master
         return master
 
     @torch.no_grad()
@@ -180,14 +184,14 @@ class Adam(torch.optim.Adam):
             with torch.enable_grad():
                 loss = closure()
         leftover = []
-        for group in self.param_groups:
+        for gi, group in enumerate(self.param_groups):
             ps = [p for p in group["params"] if p.grad is not None]
             if not self._own_kernel(group) or any(p.grad.is_sparse for p in ps):
                 leftover.append(group)
                 continue
             if not ps:
                 continue
-            master = self._shared_step(group, ps)
+            master = self._shared_step(gi, group, ps)
             if master is None:
                 leftover.append(group)
                 continue
@@ -205,7 +209,7 @@ class Adam(torch.optim.Adam):
             grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in ps]
             n = len(ps)
             arr = lambda vals: (ctypes.c_int64 * n)(*vals)
-            lr = _lr_scalar(self._lr_dev, group, dev, "Adam")
+            lr = _lr_scalar(self._lr_dev, gi, group, dev, "Adam")
             b1, b2 = group["betas"]
             rc = lib.raw("dc_adam_step")(arr(p.data_ptr() for p in ps), arr(g.data_ptr() for g in grads),
                                          arr(self.state[p]["exp_avg"].data_ptr() for p in ps),
@@ -214,6 +218,8 @@ class Adam(torch.optim.Adam):
                                          float(group["eps"]), float(group["weight_decay"]), torch.cuda.current_stream().cuda_stream)
             if rc != 0:
                 raise RuntimeError(f"dc_adam_step failed (rc={rc}): {lib.last_error()}")
+            if not any(p.numel() for p in ps):
+                master.add_(1.0)            # (no workgroup to advance it: torch counts the step of empty parameters too)
         if leftover:
             groups = self.param_groups
             try:
