@@ -2,7 +2,7 @@
 // accumulation; two multiply paths over the same tiles, staging, prologues and epilogues:
 //   * split products (X3, the default on whole 128-column tiles): every fp32 fragment is cut in registers into three bfloat16
 //     planes and each accumulator gets six v_mfma_f32_32x32x16_bf16 per 16-deep k-step -- error against fp64 at or below the
-//     exact chain's, 1.24-1.31 x its speed (comment at split_pair / the X3 loop below);
+//     exact chain's, 1.24-1.31 x its speed (comment at split_pair in gemm_split.h / the X3 loop below);
 //   * the exact chain described next (v_mfma_f32_32x32x2_f32, bitwise an fmaf chain): ragged shapes, 64-column tiles,
 //     option DC_OPT_GEMM_EXACT.
 //
@@ -29,9 +29,11 @@
 // two 128-byte row pieces -- store-issue bound.  Each wave instead transposes its tile through LDS (the operand
 // buffers are dead by then) and writes whole rows with 16-byte stores (r02a: the dword epilogue cost ~20 % of a
 // 128 x 128 x 512 workgroup's time).
-// The weight gradient dW[M,N] = dY[R,M]^T X[R,N] (both operands reduction-major, R = points) runs through the same
-// kernel with the reduction split over row slabs (grid.y) into per-slab partial tiles, summed in slab order by
-// gemm_tn_reduce_kernel (gemm_tn.hip): deterministic, no atomics.
+// The weight gradient dW[M,N] = dY[R,M]^T X[R,N] (both operands reduction-major, R = points) has the reduction split over row
+// slabs (grid.y) into per-slab partial tiles, summed in slab order by gemm_tn_reduce_kernel (gemm_tn.hip): deterministic, no
+// atomics.  Whole tiles with 128 rows run gemm_tn_planes.hip (operands cut into bf16 planes once, at the LDS store; same bits as
+// this kernel's split loop); 64-row tiles, ragged shapes, the exact chain and switch DC_OPT_TN_PLANES = 1 run this kernel
+// (dc_tn_lds_launch below).
 //
 // Fused epilogues (forward): the per-column sum / sum of squares of the tile (BatchNorm statistics of the
 // Linear output, nn/nonlin.py:24-35), or of the per-point vector norms of an interleaved (P_c, Q_c) output
@@ -47,11 +49,12 @@
 #include "common.h"
 #include "nn_math.h"
 #include "colreduce.h"
+#include "gemm_split.h"
+#include "gemm_tn_planes.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace dcsplit;
 
 #ifndef DC_X3_PLAIN
 #define DC_X3_PLAIN 2          // split-product loop of the plain products: 1 = simple, 2 = pipelined (two plane sets)
@@ -93,16 +96,6 @@ struct GemmP {
     const unsigned short* Bp; long bps;
 };
 
-// Fast-path load: buffer_load through a descriptor built from the wave-uniform tile origin (SGPRs), a wave-uniform
-// byte offset (soff: which of the thread's loads) and ONE 32-bit per-thread byte offset per operand (voff) -- no 64-bit
-// per-load address registers and no VALU address arithmetic in the K loop.  num_records = 2^31: no range clipping.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 uload4(const float* ubase, unsigned voff, unsigned soff = 0) {
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ubase), 0, 0x7FFFFFFF, 0x00020000);
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0);
-    return __builtin_bit_cast(f32x4, v);
-}
-
 // Guarded forms (ragged shapes): the SAME loads with the per-thread offset of an out-of-range element replaced by
 // 2^31 -- beyond num_records, so the hardware range check returns 0.0 without a memory access and the K loop stays
 // branch-free.  Vector form: all four elements in or out together (extents and leading dimensions multiples of 4,
@@ -128,46 +121,7 @@ __device__ __forceinline__ f32x4 pload4(const float* ubase, unsigned voff, unsig
     return gload4s(ubase, voff, soff, ok_row, col, ncols);
 }
 
-__device__ __forceinline__ f32x4 bn_bwd_vec(const f32x4 dy, const f32x4 h, const f32x4 (&cf)[5], float slope) {
-    f32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float z = fmaf(cf[0][e], h[e], cf[1][e]);
-        const float dz = dy[e] * (z > 0.f ? 1.f : slope);
-        o[e] = fmaf(cf[2][e], dz, fmaf(cf[3][e], h[e], cf[4][e]));
-    }
-    return o;
-}
-
-// Workgroup barrier that orders LDS traffic only: __syncthreads() also drains the vector-memory counter (vmcnt(0)),
-// which would make every K tile wait for the global loads issued for the tiles AFTER the next one.
-__device__ __forceinline__ void lds_barrier() {
-    __builtin_amdgcn_sched_barrier(0);      // nothing is scheduled across (the MFMAs are not memory operations)
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-// ---- split products (X3): an fp32 value x is cut into three bfloat16 planes, x = hi + mid + lo up to 2^-25 |x|
-// (hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid); both differences are exact in fp32), and the product
-// of two fp32 operands is accumulated from the six partial products of weight >= 2^-16 (lo.hi, hi.lo, mid.mid, mid.hi,
-// hi.mid, hi.hi) on the bf16 matrix pipe with fp32 accumulation: v_mfma_f32_32x32x16_bf16 retires 16x the
-// multiply-adds per cycle of v_mfma_f32_32x32x2_f32, so six of them cost 6/16 of the exact chain.  The dropped terms
-// (mid.lo, lo.mid, lo.lo) are below 2^-23 of |a||b|, and each instruction sums 16 products before the one rounding
-// into the accumulator: measured error against fp64 is BELOW the fp32 chain's (profiles/r03o_bf16x3_lab.txt).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 struct Planes { u32x4 h, m, l; };       // 8 bfloat16 each: element j of the MFMA operand = k index 8 (lane >> 5) + j
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {      // v_cvt_pk_bf16_f32 (round to nearest even)
-    return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){a, b}, bf16x2));
-}
-__device__ __forceinline__ void split_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-    h = pk_bf16(x0, x1);
-    const float r0 = x0 - __builtin_bit_cast(float, h << 16), r1 = x1 - __builtin_bit_cast(float, h & 0xFFFF0000u);
-    m = pk_bf16(r0, r1);
-    const float s0 = r0 - __builtin_bit_cast(float, m << 16), s1 = r1 - __builtin_bit_cast(float, m & 0xFFFF0000u);
-    l = pk_bf16(s0, s1);
-}
 __device__ __forceinline__ void split8(const f32x4 a, const f32x4 b, Planes& o) {
     const float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
 #pragma unroll
@@ -177,10 +131,6 @@ __device__ __forceinline__ void split8(const f32x4 a, const f32x4 b, Planes& o) 
         o.h[j] = h; o.m[j] = m; o.l[j] = l;
     }
 }
-__device__ __forceinline__ f32x16 mfma_bf16(const u32x4 a, const u32x4 b, const f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
 template <int BM, int BN, int AL, int BL, int MODE, int EPI, int PRO = 0, int X3 = 0, int BP = 0>
 __device__ __forceinline__ void gemm_body(const GemmP& p, const unsigned bid, const unsigned gemm_blocks) {
     static_assert(!BP || (X3 == 2 && AL == A_MK && BL == B_NK && MODE == 0), "pre-split B planes: pipelined split loop, K-contiguous operands, whole tiles");
@@ -1151,6 +1101,15 @@ DcTnPlan dc_tn_lds_plan(long R, int M, int N) {
     pl.slabs = (int)((R + rps - 1) / rps);
     return pl;
 }
+// Where the plane-image kernel runs faster than gemm_kernel (profiles/tn_planes_ab.txt): 128-row tiles in launches of more than
+// one workgroup per CU, plain and prologue forms (128 x 128: 0.81-0.89 of gemm_kernel's split loop, 128 x 64: 0.81 of the exact
+// chain; inside the step 217.8 -> 185.3, 75.9 -> 66.9, 63.4 -> 60.2 us).  Not faster, and left on gemm_kernel:
+//   * 64 x 64 tiles (the plans of small outputs and of few rows): 15.0 vs 20.1 us at 65536 x 64 x 64, 21.5 vs 28.7 us for the
+//     prologue form at 32768 x 128 x 128 -- one 32 x 32 accumulator per wave puts the 16 split items of a tile against 6 MFMAs per
+//     k-step, and only two of the four waves stage;
+//   * 128 x 128 tiles with one workgroup per CU (outputs of 2 tiles x 128 slabs, 8 K tiles per workgroup): inside the step
+//     28.1 -> 30.4 and 28.2 -> 29.4 us -- its two barriers per K tile count on a second workgroup of the CU to fill them.
+static bool tn_planes_faster(Tile t, long workgroups) { return t.bm == 128 && workgroups > 256; }
 int dc_tn_lds_launch(const float* A, long lda, const float* B, long ldb, long R, int M, int N, float* partial,
                      hipStream_t s, const float* h, long ldh, const float* coefs, float slope) {
     const DcTnPlan pl = dc_tn_lds_plan(R, M, N);
@@ -1172,12 +1131,18 @@ int dc_tn_lds_launch(const float* A, long lda, const float* B, long ldb, long R,
                        al16p(partial);
     bool a4 = M % 4 == 0 && lda % 4 == 0 && al16p(A);                       // reduction-major: 4-vectors run along M / N
     const bool b4 = N % 4 == 0 && ldb % 4 == 0 && al16p(B);
-    if (h) {
-        a4 = a4 && ldh % 4 == 0 && al16p(h);
-        launch_fast<A_KM, B_KN, EPI_NONE, 1>(p, t, tiles_m, pl.slabs, load_mode(whole && al16p(coefs), a4, b4), s);
-    } else {
-        launch_fast<A_KM, B_KN, EPI_NONE>(p, t, tiles_m, pl.slabs, load_mode(whole, a4, b4), s);
+    if (h) a4 = a4 && ldh % 4 == 0 && al16p(h);
+    const int mode = load_mode(whole && (!h || al16p(coefs)), a4, b4);
+    // Whole, aligned tiles: bf16 plane images in LDS (gemm_tn_planes.hip) where tn_planes_faster() has them ahead; switch 12 = 1 keeps
+    // every shape on gemm_kernel, the exact chain (switch 3) never goes through the plane kernel.
+    const int sw = dc_option(DC_OPT_TN_PLANES);
+    if (mode == 0 && dc_option(DC_OPT_GEMM_EXACT) == 0 && (sw == 2 || (sw == 0 && tn_planes_faster(t, tiles_m * p.tiles_n * pl.slabs)))) {
+        const DcTnPlanesP q{A, lda, B, ldb, partial, M, N, R, pl.rows_per_slab, h, ldh, coefs, slope};
+        (void)dc_tn_planes_launch(t.bm, t.bn, q, pl.slabs, s);       // (false: the LDS opt-in failed, reported by DC_CHECK_LAUNCH)
+        return pl.slabs;
     }
+    if (h) launch_fast<A_KM, B_KN, EPI_NONE, 1>(p, t, tiles_m, pl.slabs, mode, s);
+    else launch_fast<A_KM, B_KN, EPI_NONE>(p, t, tiles_m, pl.slabs, mode, s);
     return pl.slabs;
 }
 

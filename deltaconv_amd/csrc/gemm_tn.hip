@@ -302,7 +302,8 @@ Plan make_plan(long R, int M, int N) {
 
 }  // namespace
 
-// LDS-staged variant (gemm.hip): full-line 16-byte loads into LDS, fragments from LDS, 16-byte stores
+// LDS-staged variants: gemm.hip (fp32 tiles in LDS: full-line 16-byte loads, fragments from LDS, 16-byte stores) and, for whole
+// tiles with 128 rows, gemm_tn_planes.hip (bf16 plane images in LDS, split once per element); dc_tn_lds_launch picks
 struct DcTnPlan { int bm, bn, slabs; long rows_per_slab; };
 DcTnPlan dc_tn_lds_plan(long R, int M, int N);
 int dc_tn_lds_launch(const float* A, long lda, const float* B, long ldb, long R, int M, int N, float* partial, hipStream_t s,

@@ -44,7 +44,10 @@ const char* dc_last_error(void);
  * 8: value 1 = CSC count / scan / fill by one workgroup per cloud (round 3) instead of eight column ranges per cloud;
  * 9: value 1 = ignore pre-split weight planes (every product splits its weight operand in the K loop, as in round 3);
  * 10: value 1 = cross-entropy of <= 64 rows through the two-launch form (same bits as the one-launch form);
- * 11: value 1 = dense products with fewer than 256 workgroups keep 128-column tiles (round-6 rule off). */
+ * 11: value 1 = dense products with fewer than 256 workgroups keep 128-column tiles (round-6 rule off);
+ * 12: weight gradients on whole tiles: 0 = the plane-image kernel (operands cut into bf16 planes once, at the LDS store) on the
+ * launches it runs faster (128-row tiles, more than one workgroup per CU), 1 = the fp32-tile kernel everywhere (fallback, A/B partner), 2 = the plane-image kernel on every
+ * whole tile (lab). */
 int dc_set_option(int32_t key, int32_t value);
 
 /* Deferred finalisers (round 6): a column reduction is two launches (partials, finaliser).  Between dc_finalisers_begin() and
