@@ -1,0 +1,301 @@
+"""Device-resident datasets: the prepared dataset lives in HBM, ONE kernel launch builds a training batch from it --
+gather of the chosen clouds, augmentation with on-device draws, ``pos / norm / x / batch / ptr / y / category`` written
+straight into the batch's tensors (csrc/batch.hip: ``dc_batch_assemble``).
+
+What it replaces: the host side of the reference's input pipelines (experiments/train_modelnet.py:37-50,99,
+train_shapenet.py:36-50, train_scanobjectnn.py:47-62, train_shapeseg.py:37-61, train_shrec.py:37-52) -- a Python
+``transform`` per shape, a Python collate per batch, an upload from pageable memory per batch.  Every dataset of those
+scripts fits in HBM many times over (ModelNet40 at 1024 points with normals: 242 MB).
+
+    store = DeviceDataset.from_dataset(train_dataset, device)          # ds.transform is NOT run; the loader's is
+    loader = DeviceLoader(store, 32, shuffle=True, drop_last=True,
+                          transform=[T.RandomScale((4 / 5, 5 / 4)), T.RandomTranslateGlobal(0.1)], seed=1)
+    for epoch in range(epochs):
+        loader.set_epoch(epoch)
+        for batch in loader: ...                                        # deltaconv_amd.Batch on the device, no host sync
+    step = GraphedTrainStep(model, loss_fn, loader.static_batch(), opt)
+    for _ in loader.into(step.static): step()                           # assembled in place, then the replay
+
+The permutation of an epoch is a function of ``(seed, epoch)``, drawn on the host and uploaded once per epoch; the
+augmentation draws are a function of ``(seed, step = epoch * len(loader) + i, dataset index of the cloud, op, point)``
+(csrc/batch_math.h), so a run is reproducible from ``(seed, epoch)`` and a cloud's augmented rows do not depend on the
+batch it lands in.  There is no CPU path: a transform the kernel does not implement raises ``ValueError``.
+"""
+import ctypes
+import numbers
+
+import numpy as np
+import torch
+
+from . import transforms as T
+from ._lib import lib
+from .data import Batch
+from .geometry.graph import PtrInfo
+
+__all__ = ["DeviceDataset", "DeviceLoader", "RandomJitter", "translate_transforms",
+           "OP_SCALE", "OP_ROTATE", "OP_TRANSLATE", "OP_NORMAL_JITTER", "OP_POINT_JITTER", "MAX_OPS"]
+
+# op codes of csrc/batch_math.h
+OP_SCALE, OP_ROTATE, OP_TRANSLATE, OP_NORMAL_JITTER, OP_POINT_JITTER = 1, 2, 3, 4, 5
+MAX_OPS = 8
+
+
+class RandomJitter:
+    """Per-point, per-axis offsets uniform in ``(-translate, translate)`` added to ``pos``: torch_geometric's
+    ``RandomTranslate`` (the jitter of experiments/train_scanobjectnn.py:49), with its random-number consumption -- one
+    ``uniform_`` of n values per axis, in axis order."""
+
+    def __init__(self, translate):
+        self.translate = translate
+
+    def __call__(self, data):
+        n, dim = data.pos.size()
+        t = [self.translate] * dim if isinstance(self.translate, numbers.Number) else list(self.translate)
+        assert len(t) == dim
+        ts = [data.pos.new_empty(n).uniform_(-abs(a), abs(a)) for a in t]
+        data.pos = data.pos + torch.stack(ts, dim=-1)
+        return data
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({self.translate})"
+
+
+def _three(t, what):
+    t = [t] * 3 if isinstance(t, numbers.Number) else list(t)
+    if len(t) != 3:
+        raise ValueError(f"{what}: one value or one per axis of a 3-D cloud, got {t}")
+    return tuple(abs(float(a)) for a in t)
+
+
+def translate_transforms(transform, has_norm=True):
+    """``None`` | a transform | a ``Compose`` / list / tuple of them -> the kernel's op list ``[(code, (p0, p1, p2)), ...]``,
+    in order.  Anything but RandomScale / RandomRotate / RandomTranslateGlobal / RandomNormals / RandomJitter raises
+    ``ValueError`` naming it; so does RandomNormals on a store without normals."""
+    if transform is None:
+        seq = []
+    elif isinstance(transform, (list, tuple)):
+        seq = list(transform)
+    elif hasattr(transform, "transforms"):
+        seq = list(transform.transforms)
+    else:
+        seq = [transform]
+    ops = []
+    for t in seq:
+        if type(t) is T.RandomScale:
+            ops.append((OP_SCALE, (float(t.scales[0]), float(t.scales[1]), 0.0)))
+        elif type(t) is T.RandomRotate:
+            if t.axis not in (0, 1, 2):
+                raise ValueError(f"{t!r}: axis must be 0, 1 or 2")
+            ops.append((OP_ROTATE, (float(t.degrees[0]), float(t.degrees[1]), float(t.axis))))
+        elif type(t) is T.RandomTranslateGlobal:
+            ops.append((OP_TRANSLATE, _three(t.translate, repr(t))))
+        elif type(t) is T.RandomNormals:
+            if not has_norm:
+                raise ValueError(f"{t!r}: the store has no normals")
+            ops.append((OP_NORMAL_JITTER, _three(t.translate, repr(t))))
+        elif type(t) is RandomJitter:
+            ops.append((OP_POINT_JITTER, _three(t.translate, repr(t))))
+        else:
+            raise ValueError(f"DeviceLoader: no device form of transform {t!r} ({type(t).__name__}); it takes RandomScale, "
+                             "RandomRotate, RandomTranslateGlobal, RandomNormals and RandomJitter (there is no CPU fallback)")
+    if len(ops) > MAX_OPS:
+        raise ValueError(f"DeviceLoader: at most {MAX_OPS} augmentation ops, got {len(ops)}")
+    return ops
+
+
+class DeviceDataset:
+    """All clouds of a dataset concatenated on the device (the "store") + their sizes on the host."""
+
+    def __init__(self, pos, ptr, sizes, norm=None, x=None, y_point=None, y_cloud=None, category=None):
+        self.pos, self.norm, self.x, self.y_point, self.y_cloud, self.category = pos, norm, x, y_point, y_cloud, category
+        self.ptr = ptr                                   # int64 [S+1], device
+        self.sizes = np.asarray(sizes, dtype=np.int64)   # host
+        self.device = pos.device
+
+    def __len__(self):
+        return int(self.sizes.shape[0])
+
+    @classmethod
+    def from_dataset(cls, ds, device):
+        """ds: a dataset with ``.items`` (ModelNet / ScanObjectNN / ShapeNet / ShapeSeg; its ``transform`` is not run) or any
+        sequence of ``Data``.  Attributes taken: ``pos``, ``norm`` (or ``normal``), ``x``, ``y`` (one per cloud or one per
+        point), ``category`` -- each either on every item or on none, as ``collate`` treats them."""
+        items = list(ds.items if hasattr(ds, "items") and not callable(ds.items) else ds)
+        if not items:
+            raise ValueError("DeviceDataset: empty dataset")
+
+        def column(name):
+            vals = [getattr(d, name, None) for d in items]
+            return vals if all(v is not None for v in vals) else None
+
+        pos = [d.pos for d in items]
+        sizes = [int(p.shape[0]) for p in pos]
+        for p in pos:
+            if p.dim() != 2 or p.shape[1] != 3:
+                raise ValueError(f"DeviceDataset: pos must be [n, 3], got {tuple(p.shape)}")
+        norm = column("norm") or column("normal")
+        x = column("x")
+        if x is not None:
+            x = [v.reshape(v.shape[0], -1) for v in x]
+        ys, y_point, y_cloud = column("y"), None, None
+        if ys is not None:
+            ys = [(v if torch.is_tensor(v) else torch.tensor([v])).reshape(-1) for v in ys]
+            if any(v.is_floating_point() for v in ys):
+                raise ValueError("DeviceDataset: labels must be integers")
+            if all(v.numel() == 1 for v in ys):
+                y_cloud = torch.cat(ys).long()
+            elif all(v.numel() == n for v, n in zip(ys, sizes)):
+                y_point = torch.cat(ys).long()
+            else:
+                raise ValueError("DeviceDataset: y must hold one label per cloud or one per point")
+        cats = column("category")
+        category = torch.stack([c.reshape(-1) for c in cats]).float() if cats is not None else None
+        for name, col in (("norm", norm), ("x", x)):
+            if col is not None and any(v.shape[0] != n for v, n in zip(col, sizes)):
+                raise ValueError(f"DeviceDataset: {name} must have one row per point")
+        ptr = torch.zeros(len(items) + 1, dtype=torch.int64)
+        ptr[1:] = torch.cumsum(torch.tensor(sizes, dtype=torch.int64), 0)
+        up = lambda t: None if t is None else t.contiguous().to(device)
+        f32 = lambda col: None if col is None else torch.cat(col).float()
+        return cls(up(f32(pos)), up(ptr), sizes, up(f32(norm)), up(f32(x)), up(y_point), up(y_cloud), up(category))
+
+
+def epoch_permutation(n, seed, epoch, shuffle=True):
+    """The order of the n clouds in `epoch`: a function of (seed, epoch) only; ``arange`` without shuffling."""
+    if not shuffle:
+        return np.arange(n, dtype=np.int64)
+    return np.random.Generator(np.random.Philox(key=[int(seed), int(epoch)])).permutation(n).astype(np.int64)
+
+
+class DeviceLoader:
+    def __init__(self, store, batch_size, shuffle=False, drop_last=False, transform=None, seed=0, rank=0, world=1):
+        if batch_size < 1 or not 0 <= rank < world:
+            raise ValueError("DeviceLoader: batch_size >= 1 and 0 <= rank < world")
+        if not 0 <= int(seed) < 2 ** 32:
+            raise ValueError("DeviceLoader: seed in [0, 2^32)")
+        self.store, self.batch_size, self.shuffle, self.drop_last = store, int(batch_size), shuffle, drop_last
+        self.seed, self.rank, self.world, self.epoch = int(seed), int(rank), int(world), 0
+        self.ops = translate_transforms(transform, has_norm=getattr(store, "norm", None) is not None)
+        n = len(self.ops)
+        self._codes = (ctypes.c_int32 * max(n, 1))(*[c for c, _ in self.ops])
+        self._params = (ctypes.c_float * max(3 * n, 1))(*[v for _, p in self.ops for v in p])
+        self.share = len(store) // self.world            # clouds per rank and epoch: equally long shares
+        self._perm_dev = (None, None)                    # (epoch, this rank's share of its permutation on the device)
+
+    def __len__(self):
+        return self.share // self.batch_size if self.drop_last else -(-self.share // self.batch_size)
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def rank_share(self, epoch, rank=None):
+        """Host index array of one rank's share of the epoch: the permutation is the same on every rank, cut to a multiple
+        of `world` (the last ``len(store) % world`` clouds of the epoch's order sit out), rank r takes every world-th."""
+        perm = epoch_permutation(len(self.store), self.seed, epoch, self.shuffle)
+        return perm[:self.share * self.world][(self.rank if rank is None else rank)::self.world]
+
+    def batch_indices(self, epoch=None):
+        """The dataset indices of every batch of `epoch` (default: the current one) on this rank, as host lists."""
+        share = self.rank_share(self.epoch if epoch is None else epoch)
+        bs = self.batch_size
+        return [share[i * bs:(i + 1) * bs].tolist() for i in range(len(self))]
+
+    # ---- the launch -----------------------------------------------------------------------------------------------------
+    def _shape(self, sizes):
+        st = self.store
+        nt, b = int(sizes.sum()), int(sizes.shape[0])
+        return {"pos": (nt, 3), "norm": None if st.norm is None else (nt, 3),
+                "x": None if st.x is None else (nt, st.x.shape[1]),
+                "y": (nt,) if st.y_point is not None else ((b,) if st.y_cloud is not None else None),
+                "category": None if st.category is None else (b, st.category.shape[1])}
+
+    def _new_batch(self, sizes):
+        dev, sh = self.store.device, self._shape(sizes)
+        mk = lambda s, dt: None if s is None else torch.empty(s, dtype=dt, device=dev)
+        out = Batch(mk(sh["pos"], torch.float32), torch.empty(sh["pos"][0], dtype=torch.int64, device=dev),
+                    mk(sh["norm"], torch.float32), mk(sh["x"], torch.float32), mk(sh["y"], torch.int64),
+                    mk(sh["category"], torch.float32), num_graphs=sizes.shape[0])
+        out._ptr = torch.empty(sizes.shape[0] + 1, dtype=torch.int32, device=dev)
+        return out
+
+    def _assemble(self, out, idx_dev, sizes, step):
+        """One launch: the clouds idx_dev (device int64 [B], sizes known on the host) into the tensors of `out`."""
+        st = self.store
+        b, nt, mx = int(sizes.shape[0]), int(sizes.sum()), int(sizes.max())
+        lib.call("dc_batch_assemble", st.pos, st.norm, st.x, 0 if st.x is None else st.x.shape[1], st.y_point, st.y_cloud,
+                 st.category, 0 if st.category is None else st.category.shape[1], st.ptr, len(st), idx_dev, b, nt, mx,
+                 self._codes, self._params, len(self.ops), self.seed, int(step), out.pos, out.norm, out.x, out.batch, out._ptr,
+                 out.y, out.category)
+        out._ptr_info = PtrInfo(out._ptr, b, mx, int(sizes.min()))     # the host knows the sizes: no sync in the model
+        return out
+
+    def assemble(self, indices, step=0, out=None):
+        """The batch of the clouds `indices` (host list / array of dataset indices) at augmentation step `step`."""
+        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+        if idx.size == 0 or idx.min() < 0 or idx.max() >= len(self.store):
+            raise ValueError("DeviceLoader.assemble: indices must be a non-empty list of dataset indices")
+        sizes = self.store.sizes[idx]
+        out = self._new_batch(sizes) if out is None else out
+        return self._assemble(out, torch.from_numpy(idx).to(self.store.device), sizes, step)
+
+    def _epoch(self, target=None):
+        epoch = self.epoch
+        share = self.rank_share(epoch)
+        if self._perm_dev[0] != (epoch, self.shuffle):
+            self._perm_dev = ((epoch, self.shuffle), torch.from_numpy(np.ascontiguousarray(share)).to(self.store.device))
+        perm_dev, bs, nb = self._perm_dev[1], self.batch_size, len(self)
+        want = None if target is None else self._batch_shape(target)
+        for i in range(nb):
+            sizes = self.store.sizes[share[i * bs:(i + 1) * bs]]
+            if target is not None:
+                sh = dict(self._shape(sizes), batch=(int(sizes.sum()),), ptr=(sizes.shape[0] + 1,))
+                if sh != want or not np.array_equal(sizes, self._static_sizes(target)):
+                    raise ValueError(f"DeviceLoader.into: batch {i} of epoch {epoch} does not have the shape of the static batch "
+                                     f"({sh} vs {want}, or other cloud sizes); in-place assembly needs equal shapes "
+                                     "(equal-size clouds, drop_last=True)")
+            out = self._new_batch(sizes) if target is None else target
+            yield self._assemble(out, perm_dev[i * bs:(i + 1) * bs], sizes, epoch * nb + i)
+        self.epoch = epoch + 1
+
+    def __iter__(self):
+        return self._epoch()
+
+    # ---- in place, in front of a captured step ---------------------------------------------------------------------------
+    @staticmethod
+    def _batch_shape(batch):
+        sh = lambda t: None if t is None else tuple(t.shape)
+        return {"pos": sh(batch.pos), "norm": sh(batch.norm), "x": sh(batch.x), "y": sh(batch.y),
+                "category": sh(batch.category), "batch": sh(batch.batch), "ptr": sh(batch.ptr)}
+
+    @staticmethod
+    def _static_sizes(batch):
+        sizes = getattr(batch, "_dc_sizes", None)
+        if sizes is None:                       # a batch from elsewhere: one host read, once
+            ptr = batch.ptr.cpu().numpy().astype(np.int64)
+            sizes = batch._dc_sizes = ptr[1:] - ptr[:-1]
+        return sizes
+
+    def static_batch(self):
+        """A batch of the loader's full shape (the first batch of epoch 0, unaugmented order does not matter: it is
+        overwritten by ``into``), to hand to ``GraphedTrainStep`` as its sample batch."""
+        if len(self) == 0:
+            raise ValueError("DeviceLoader.static_batch: the loader has no full batch")
+        idx = self.rank_share(0)[:self.batch_size]
+        out = self.assemble(idx, step=0)
+        out._dc_sizes = self.store.sizes[idx].copy()
+        return out
+
+    def into(self, static):
+        """Iterate the current epoch while assembling IN PLACE into the tensors of `static` (``step.static`` of a
+        GraphedTrainStep): one launch per batch in place of the copy launch of ``GraphedTrainStep.load``, every ``data_ptr``
+        unchanged.  Yields `static` itself; call the step without a batch.  Raises when a batch of the epoch has another
+        shape or other cloud sizes than `static` (the captured step holds its cloud offsets)."""
+        if static.pos.device != self.store.device:
+            raise ValueError("DeviceLoader.into: the static batch lives on another device than the store")
+        for name, dt in (("pos", torch.float32), ("norm", torch.float32), ("x", torch.float32), ("y", torch.int64),
+                         ("category", torch.float32), ("batch", torch.int64)):
+            t = getattr(static, name, None)
+            if t is not None and (t.dtype != dt or not t.is_contiguous()):
+                raise ValueError(f"DeviceLoader.into: static.{name} must be contiguous {dt}")
+        static.ptr                               # materialised once (a batch from elsewhere computes it here)
+        return self._epoch(target=static)

@@ -77,6 +77,9 @@ def main():
     ap.add_argument("--logdir", default="runs/modelnet_like")
     ap.add_argument("--data", default=None, help="ModelNet40 root with raw/<category>/<train|test>/*.off")
     ap.add_argument("--sampling_margin", type=int, default=8)
+    ap.add_argument("--device-loader", action="store_true",
+                    help="with --data: keep the prepared dataset on the GPU, build and augment every batch in one launch "
+                         "(deltaconv_amd.DeviceLoader) instead of per-shape transforms + collate + upload on the host")
     args = ap.parse_args()
 
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", 1), ("RANK", 0), ("LOCAL_RANK", 0)))
@@ -100,6 +103,13 @@ def main():
         aug = Compose((T.RandomScale((4 / 5, 5 / 4)), T.RandomTranslateGlobal(0.1)))
         tr = ModelNet(args.data, None, "40", True, transform=aug, pre_transform=pre)
         te = ModelNet(args.data, None, "40", False, pre_transform=pre)
+    if args.data is not None and args.device_loader:
+        # the same recipe, drawn and applied on the device; every rank takes its share of one permutation per epoch
+        train = deltaconv.DeviceLoader(deltaconv.DeviceDataset.from_dataset(tr, dev), args.batch_size, shuffle=True,
+                                       drop_last=True, transform=aug, seed=1, rank=rank, world=world)
+        test = deltaconv.DeviceLoader(deltaconv.DeviceDataset.from_dataset(te, dev), args.batch_size)
+        args.train_batches = len(train)
+    elif args.data is not None:
         sampler = torch.utils.data.distributed.DistributedSampler(tr) if world > 1 else None
         on_dev = lambda loader: (b.to(dev) for b in loader)      # each rank collates and uploads its own shard
         train_loader = DataLoader(tr, batch_size=args.batch_size, shuffle=sampler is None, sampler=sampler, drop_last=True)

@@ -93,6 +93,9 @@ def main():
     ap.add_argument("--train_batches", type=int, default=4)
     ap.add_argument("--logdir", default="runs/shapenet_like")
     ap.add_argument("--data", default=None, help="ShapeNet part root (raw/<synset>/*.txt, raw/train_test_split/*.json)")
+    ap.add_argument("--device-loader", action="store_true",
+                    help="with --data: keep the prepared dataset on the GPU, build and augment every batch in one launch "
+                         "(deltaconv_amd.DeviceLoader) instead of per-shape transforms + collate + upload on the host")
     args = ap.parse_args()
 
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", 1), ("RANK", 0), ("LOCAL_RANK", 0)))
@@ -115,6 +118,13 @@ def main():
         aug = Compose((T.RandomScale((2 / 3, 3 / 2)), T.RandomTranslateGlobal(0.2)))            # train_shapenet.py:35-38
         tr = ShapeNet(args.data, split="trainval", transform=aug, pre_transform=pre)
         te = ShapeNet(args.data, split="test", pre_transform=pre)
+    if args.data is not None and args.device_loader:
+        # the same recipe, drawn and applied on the device; every rank takes its share of one permutation per epoch
+        train = deltaconv.DeviceLoader(deltaconv.DeviceDataset.from_dataset(tr, dev), args.batch_size, shuffle=True,
+                                       drop_last=True, transform=aug, seed=1, rank=rank, world=world)
+        test = deltaconv.DeviceLoader(deltaconv.DeviceDataset.from_dataset(te, dev), args.batch_size)
+        args.train_batches = len(train)
+    elif args.data is not None:
         sampler = torch.utils.data.distributed.DistributedSampler(tr) if world > 1 else None
 
         class _OnDevice:

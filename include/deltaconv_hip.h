@@ -650,6 +650,34 @@ int dc_adam_step(const int64_t* params, const int64_t* grads, const int64_t* exp
 int dc_copy_many(const int64_t* srcs, const int64_t* dsts, const int64_t* ld_src, const int64_t* ld_dst, const int32_t* rows,
                  const int32_t* cols, int32_t count, void* stream);
 
+/* ---- device-resident datasets: batch assembly and augmentation in one launch (csrc/batch.hip, csrc/batch_math.h) -------- */
+/* Replaces the host side of the reference's input pipelines -- the per-shape `transform` of Dataset.__getitem__, the DataLoader's
+ * collate and `data.to(device)`: experiments/train_modelnet.py:37-50,99, train_shapenet.py:36-50, train_scanobjectnn.py:47-62,
+ * train_shapeseg.py:37-61, train_shrec.py:37-52.
+ * The store holds the prepared dataset on the device: store_pos [Ns,3], store_norm [Ns,3] or NULL, store_x [Ns,F] or NULL,
+ * labels store_y_point [Ns] or store_y_cloud [S] (at most one of them non-NULL), store_category [S,Cc] or NULL, offsets
+ * store_ptr [S+1].  idx [B]: DEVICE array, the clouds of this batch in slot order.  B, Nt (= sum of their sizes) and max_cloud
+ * (>= the largest of them) are known to the host; a workgroup finds the start of its cloud from the sizes of the slots before it.
+ * Outputs: pos [Nt,3], norm [Nt,3], x [Nt,F], batch [Nt] (slot of every point), ptr [B+1], y [Nt] or [B], category [B,Cc]; an output
+ * whose store counterpart is NULL is not touched (and may be NULL).  Indices outside [0, S) count as empty clouds; rows >= Nt
+ * and points beyond max_cloud are never written.
+ * Augmentation: op_codes [n_ops] / op_params [n_ops,3] are HOST arrays (n_ops <= 8), applied to every point in list order:
+ *   1 scale          (lo, hi, -)           three factors per cloud; pos *= s; norm *= 1/s, re-normalised   (random_scale.py:24-35)
+ *   2 rotate         (deg_lo, deg_hi, axis) one angle per cloud; pos @ R, norm @ R                          (random_rotate.py:28-45)
+ *   3 translate      (tx, ty, tz)          one offset per cloud and axis, uniform in (-t, t)               (random_translate_global.py)
+ *   4 normal jitter  (tx, ty, tz)          per point and axis; norm / max(|norm|, 1e-5)                    (random_normals.py:25-36)
+ *   5 point jitter   (tx, ty, tz)          per point and axis, added to pos   (PyG RandomTranslate, train_scanobjectnn.py:49)
+ * Draws: Philox-4x32-10, key (seed, 0x6261746B), counter (point in cloud | 0xFFFFFFFF for a per-cloud draw, DATASET index of the
+ * cloud, step low word, step bits 32..60 << 3 | op position); output words x, y, z serve axes 0, 1, 2 (an angle: word x);
+ * u = (r >> 8) * 2^-24, value = lo + u * (hi - lo) in fp32 without contraction; angle = degrees * (pi / 180) in fp32, sincosf.
+ * seed in [0, 2^32), step in [0, 2^61).  A cloud's augmented rows do not depend on its slot or on the rest of the batch.
+ * One launch, stream-ordered, capturable. */
+int dc_batch_assemble(const float* store_pos, const float* store_norm, const float* store_x, int32_t F,
+                      const int64_t* store_y_point, const int64_t* store_y_cloud, const float* store_category, int32_t Cc,
+                      const int64_t* store_ptr, int64_t S, const int64_t* idx, int32_t B, int64_t Nt, int32_t max_cloud,
+                      const int32_t* op_codes, const float* op_params, int32_t n_ops, int64_t seed, int64_t step, float* pos,
+                      float* norm, float* x, int64_t* batch, int32_t* ptr, int64_t* y, float* category, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
