@@ -238,7 +238,7 @@ class DeviceLoader:
         out = self._new_batch(sizes) if out is None else out
         return self._assemble(out, torch.from_numpy(idx).to(self.store.device), sizes, step)
 
-    def _epoch(self, target=None):
+    def _epoch(self, target=None, fresh_tail=False):
         epoch = self.epoch
         share = self.rank_share(epoch)
         if self._perm_dev[0] != (epoch, self.shuffle):
@@ -247,13 +247,16 @@ class DeviceLoader:
         want = None if target is None else self._batch_shape(target)
         for i in range(nb):
             sizes = self.store.sizes[share[i * bs:(i + 1) * bs]]
+            into = target
             if target is not None:
                 sh = dict(self._shape(sizes), batch=(int(sizes.sum()),), ptr=(sizes.shape[0] + 1,))
-                if sh != want or not np.array_equal(sizes, self._static_sizes(target)):
+                if fresh_tail and i == nb - 1 and sizes.shape[0] < bs:
+                    into = None                 # the short last batch of an evaluation pass: a batch of its own
+                elif sh != want or not np.array_equal(sizes, self._static_sizes(target)):
                     raise ValueError(f"DeviceLoader.into: batch {i} of epoch {epoch} does not have the shape of the static batch "
                                      f"({sh} vs {want}, or other cloud sizes); in-place assembly needs equal shapes "
                                      "(equal-size clouds, drop_last=True)")
-            out = self._new_batch(sizes) if target is None else target
+            out = self._new_batch(sizes) if into is None else into
             yield self._assemble(out, perm_dev[i * bs:(i + 1) * bs], sizes, epoch * nb + i)
         self.epoch = epoch + 1
 
@@ -285,11 +288,13 @@ class DeviceLoader:
         out._dc_sizes = self.store.sizes[idx].copy()
         return out
 
-    def into(self, static):
+    def into(self, static, fresh_tail=False):
         """Iterate the current epoch while assembling IN PLACE into the tensors of `static` (``step.static`` of a
         GraphedTrainStep): one launch per batch in place of the copy launch of ``GraphedTrainStep.load``, every ``data_ptr``
         unchanged.  Yields `static` itself; call the step without a batch.  Raises when a batch of the epoch has another
-        shape or other cloud sizes than `static` (the captured step holds its cloud offsets)."""
+        shape or other cloud sizes than `static` (the captured step holds its cloud offsets).  fresh_tail: a last batch with
+        fewer clouds than ``batch_size`` (``drop_last=False``) is yielded as a NEW batch instead of raising -- the
+        evaluation passes of deltaconv_amd.evaluate run it eagerly."""
         if static.pos.device != self.store.device:
             raise ValueError("DeviceLoader.into: the static batch lives on another device than the store")
         for name, dt in (("pos", torch.float32), ("norm", torch.float32), ("x", torch.float32), ("y", torch.int64),
@@ -298,4 +303,4 @@ class DeviceLoader:
             if t is not None and (t.dtype != dt or not t.is_contiguous()):
                 raise ValueError(f"DeviceLoader.into: static.{name} must be contiguous {dt}")
         static.ptr                               # materialised once (a batch from elsewhere computes it here)
-        return self._epoch(target=static)
+        return self._epoch(target=static, fresh_tail=fresh_tail)

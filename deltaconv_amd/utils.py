@@ -48,10 +48,15 @@ def calc_loss(pred, true, smoothing=True):
     return -((1 - eps) * picked + eps / (n_class - 1) * rest).mean()
 
 
+# the ShapeNet part tables of experiments/utils.py:28-29: parts per category and the first part label of each (16 categories,
+# 50 parts); read by calc_shape_IoU below and, as device tables, by deltaconv_amd.evaluate
+SHAPENET_SEG_NUM = (4, 2, 2, 4, 4, 3, 3, 2, 4, 2, 6, 2, 3, 3, 3, 3)
+SHAPENET_INDEX_START = (0, 4, 6, 8, 12, 16, 19, 22, 24, 28, 30, 36, 38, 41, 44, 47)
+
+
 def calc_shape_IoU(pred_np, seg_np, label, class_choice):
     """experiments/utils.py:27-51: mean part IoU per ShapeNet shape (an empty union counts as 1)."""
-    seg_num = [4, 2, 2, 4, 4, 3, 3, 2, 4, 2, 6, 2, 3, 3, 3, 3]
-    index_start = [0, 4, 6, 8, 12, 16, 19, 22, 24, 28, 30, 36, 38, 41, 44, 47]
+    seg_num, index_start = SHAPENET_SEG_NUM, SHAPENET_INDEX_START
     label = np.asarray(label).squeeze()
     ious = []
     for s in range(seg_np.shape[0]):

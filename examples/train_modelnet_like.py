@@ -80,7 +80,12 @@ def main():
     ap.add_argument("--device-loader", action="store_true",
                     help="with --data: keep the prepared dataset on the GPU, build and augment every batch in one launch "
                          "(deltaconv_amd.DeviceLoader) instead of per-shape transforms + collate + upload on the host")
+    ap.add_argument("--device-eval", action="store_true",
+                    help="with --device-loader: the per-epoch evaluation on the device (deltaconv_amd.DeviceEvaluator: captured "
+                         "forward, metrics in one launch per batch, one synchronise per pass) instead of evaluate() below")
     args = ap.parse_args()
+    if args.device_eval and not (args.data is not None and args.device_loader):
+        raise SystemExit("--device-eval evaluates from a device-resident test set: it needs --data and --device-loader")
 
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", 1), ("RANK", 0), ("LOCAL_RANK", 0)))
     torch.cuda.set_device(local)
@@ -109,6 +114,8 @@ def main():
                                        drop_last=True, transform=aug, seed=1, rank=rank, world=world)
         test = deltaconv.DeviceLoader(deltaconv.DeviceDataset.from_dataset(te, dev), args.batch_size)
         args.train_batches = len(train)
+        if args.device_eval:                 # equal-size clouds (GeodesicFPS to num_points): the full batches replay one graph
+            evaluator = deltaconv.DeviceEvaluator(model, test, task="classification")
     elif args.data is not None:
         sampler = torch.utils.data.distributed.DistributedSampler(tr) if world > 1 else None
         on_dev = lambda loader: (b.to(dev) for b in loader)      # each rank collates and uploads its own shard
@@ -126,7 +133,7 @@ def main():
         loss, acc = train_epoch(ddp, opt, train)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        test_acc = evaluate(model, test)
+        test_acc = evaluator.run()["accuracy"] if args.device_eval else evaluate(model, test)
         sched.step()
         if rank == 0:
             print(json.dumps(dict(epoch=epoch, loss=round(loss, 4), train_acc=round(acc, 4), test_acc=round(test_acc, 4),

@@ -678,6 +678,26 @@ int dc_batch_assemble(const float* store_pos, const float* store_norm, const flo
                       const int32_t* op_codes, const float* op_params, int32_t n_ops, int64_t seed, int64_t step, float* pos,
                       float* norm, float* x, int64_t* batch, int32_t* ptr, int64_t* y, float* category, void* stream);
 
+/* ---- device-side evaluation: votes, arg-max, per-class counts and part IoU in one launch (csrc/eval.hip, csrc/eval_math.h) ---- */
+/* Replaces the host side of the reference's test loops -- logits and labels copied to the host per batch, np.argmax, the Python
+ * loop over shapes and parts: experiments/utils.py:27-51 (calc_shape_IoU), test_shapenet.py:84-103 (vote sum, arg-max, metrics).
+ * logits [Nt,P] fp32 with row stride ld_logits >= P; y [Nt] labels; ptr [B+1] cloud offsets (values outside [0, Nt] are clamped).
+ * One workgroup per cloud b = rows ptr[b] .. ptr[b+1]; classification is the same entry with the batch as one cloud (ptr = [0, B]).
+ *   votes     NULL, or [Nt,P] contiguous: votes[r,c] += logits[r,c] (one fp32 add), and the predictions come from votes
+ *   pred      NULL, or [Nt]: first index of the row maximum, numpy's argmax rule (a NaN is the maximum, the first NaN wins)
+ *   cnt, hit  [B,P]: rows of the cloud labelled c, and those of them predicted c; a label outside [0, P) is in no class, is
+ *             counted in ignored [B] and indexes nothing
+ *   iou       NULL, or [B] fp64: the mean over the cloud's parts of (U == 0 ? 1 : I / U), I = #(pred == part and y == part),
+ *             U = #(pred == part or y == part): integer counts, the divisions and the sum in part order in fp64.  The parts are
+ *             part_start[k] .. part_start[k] + part_count[k] - 1 with k = arg-max of category [B,Cc] row b (part_start, part_count:
+ *             DEVICE arrays [Cc]); category NULL: all P classes.  A part outside [0, P) has an empty union (counts as 1).
+ * P in 1 .. 256 (else DC_ERR_ARG with a message); B = 0 returns DC_OK.  Integer counters in LDS, no global atomics, no
+ * floating-point atomics: the outputs are a function of the inputs only.  One launch, stream-ordered, capturable. */
+int dc_eval_metrics(const float* logits, int64_t ld_logits, float* votes, const int64_t* y, const int32_t* ptr, int32_t B,
+                    int64_t Nt, int32_t P, const float* category, int32_t Cc, const int32_t* part_start,
+                    const int32_t* part_count, int64_t* pred, double* iou, int32_t* hit, int32_t* cnt, int32_t* ignored,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
