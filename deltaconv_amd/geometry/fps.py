@@ -1,6 +1,9 @@
 """Geodesic farthest-point sampling (reference: deltaconv/geometry/fps.py:5-17 over the pybind module
 of deltaconv/cpp).  Same validation, same return value; the native part is the dependency-free C++
-restatement in deltaconv_amd/csrc_host/fps.cpp behind a C ABI (include/deltaconv_host.h)."""
+restatement in deltaconv_amd/csrc_host/fps.cpp behind a C ABI (include/deltaconv_host.h).
+
+``geodesic_fps_batch`` is the same sampler for a batch of clouds that already live on the device (csrc/fps.hip behind
+``dc_geodesic_fps_batch``): the same picks as ``geodesic_fps`` from the same start point, all clouds in two launches."""
 import ctypes
 import os
 import warnings
@@ -40,3 +43,88 @@ def geodesic_fps(points, n_samples, seed=None):
     if rc != 0:
         raise ValueError("geodesic_fps: bad arguments")
     return out.squeeze()
+
+
+FPS_MAX_POINTS = 16384        # DC_FPS_MAX_POINTS: a cloud's distance vector lives in the LDS of one workgroup (csrc/fps_math.h)
+
+
+def fps_starts(sizes, seed=None, first=0):
+    """The start point of every cloud: ``sizes[i]`` points, cloud index ``first + i``.  With a seed it is a function of
+    ``(seed, cloud index, size)`` only -- a counter-based generator keyed by the pair, as ``loader.epoch_permutation`` keys its
+    own by (seed, epoch) -- so it does not depend on how clouds are grouped into launches; ``seed=None`` draws at random like
+    the reference (sampling.cpp:34-40).  -> int32 [len(sizes)]"""
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
+    if sizes.size and sizes.min() < 1:
+        raise ValueError("geodesic_fps_batch: empty cloud")
+    if seed is None:
+        return np.random.default_rng().integers(0, sizes).astype(np.int32)
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("geodesic_fps_batch: seed in [0, 2^64)")
+    return np.array([np.random.Generator(np.random.Philox(key=[int(seed), int(first) + i])).integers(0, int(n))
+                     for i, n in enumerate(sizes)], dtype=np.int32).reshape(-1)
+
+
+def _fps_device(pos, ptr_host, n_samples, start_host):
+    """One launch pair over the clouds ptr_host (numpy int64 [B+1], ptr_host[0] = 0) of pos -> int32 [B, n_samples] on the device."""
+    import torch
+    from .._lib import lib
+    b = int(ptr_host.shape[0]) - 1
+    out = torch.empty((b, int(n_samples)), dtype=torch.int32, device=pos.device)
+    if b == 0:
+        return out
+    ptr_host = np.ascontiguousarray(ptr_host, dtype=np.int64)
+    start_host = np.ascontiguousarray(start_host, dtype=np.int32)
+    need = int(lib.raw("dc_geodesic_fps_workspace_bytes")(int(ptr_host[-1])))
+    ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=pos.device)
+    sizes = ptr_host[1:] - ptr_host[:-1]
+    lib.call("dc_geodesic_fps_batch", pos, 1 if pos.dtype == torch.float64 else 0, ctypes.c_void_p(ptr_host.ctypes.data), b,
+             int(sizes.max()), int(n_samples), ctypes.c_void_p(start_host.ctypes.data), out, ws, need)
+    return out
+
+
+def _fps_launches(pos, ptr_host, n_samples, start_host, clouds_per_launch=1024):
+    """The clouds in groups of at most `clouds_per_launch` (the workspace holds 132 bytes per point of a group) -> int32 [B, n_samples]."""
+    import torch
+    b = int(ptr_host.shape[0]) - 1
+    if b <= clouds_per_launch:
+        return _fps_device(pos, ptr_host, n_samples, start_host)
+    parts = []
+    for lo in range(0, b, clouds_per_launch):
+        hi = min(b, lo + clouds_per_launch)
+        parts.append(_fps_device(pos[int(ptr_host[lo]):int(ptr_host[hi])], ptr_host[lo:hi + 1] - ptr_host[lo], n_samples,
+                                 start_host[lo:hi]))
+    return torch.cat(parts)
+
+
+def geodesic_fps_batch(pos, ptr, n_samples, start=None, seed=None):
+    """Geodesic farthest-point sampling of every cloud of a batch on the device (reference: transforms/geodesic_fps.py:14-43
+    over cpp/sampling.cpp:5-81, one host call per shape).
+
+    pos: DEVICE float32 / float64 [N,3]; ptr: int64 [B+1] cloud offsets (tensor on any device, or array), ptr[0] = 0 and
+    ptr[B] = N.  -> DEVICE int64 [B, n_samples], ids local to the cloud: row b is what ``geodesic_fps(pos[ptr[b]:ptr[b+1]],
+    n_samples)`` returns when it starts from the same point.  ``start``: the first sample of every cloud (B ids local to the
+    cloud); otherwise ``fps_starts(sizes, seed)``.  Clouds of more than ``FPS_MAX_POINTS`` = 16 384 points, empty clouds, a
+    start outside its cloud and host tensors raise ``ValueError``; there is no CPU path (``geodesic_fps`` is the host sampler)."""
+    import torch
+    if not torch.is_tensor(pos) or not pos.is_cuda:
+        raise ValueError("geodesic_fps_batch: `pos` must be a tensor on a HIP device (geodesic_fps samples host arrays)")
+    if pos.dim() != 2 or pos.shape[1] != 3 or pos.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"geodesic_fps_batch: `pos` must be float32 / float64 [N,3], got {pos.dtype} {tuple(pos.shape)}")
+    ptr_host = (ptr.detach().cpu().numpy() if torch.is_tensor(ptr) else np.asarray(ptr)).astype(np.int64).reshape(-1)
+    if ptr_host.size < 1 or ptr_host[0] != 0 or ptr_host[-1] != pos.shape[0]:
+        raise ValueError("geodesic_fps_batch: `ptr` must hold B+1 offsets from 0 to the number of points")
+    if int(n_samples) < 1:
+        raise ValueError("geodesic_fps_batch: n_samples >= 1")
+    sizes = ptr_host[1:] - ptr_host[:-1]
+    if sizes.size and sizes.min() < 1:
+        raise ValueError("geodesic_fps_batch: empty cloud")
+    if sizes.size and sizes.max() > FPS_MAX_POINTS:
+        raise ValueError(f"geodesic_fps_batch: a cloud of {int(sizes.max())} points; the device sampler takes at most "
+                         f"{FPS_MAX_POINTS} per cloud (use geodesic_fps on the host for larger ones)")
+    if start is None:
+        start_host = fps_starts(sizes, seed)
+    else:
+        start_host = (start.detach().cpu().numpy() if torch.is_tensor(start) else np.asarray(start)).astype(np.int64).reshape(-1)
+        if start_host.shape != sizes.shape or (start_host < 0).any() or (start_host >= sizes).any():
+            raise ValueError("geodesic_fps_batch: `start` must hold one point of every cloud (ids local to the cloud)")
+    return _fps_launches(pos.contiguous(), ptr_host, n_samples, start_host).long()

@@ -116,10 +116,11 @@ class DeviceDataset:
         return int(self.sizes.shape[0])
 
     @classmethod
-    def from_dataset(cls, ds, device):
+    def from_dataset(cls, ds, device, fps=None, fps_seed=None):
         """ds: a dataset with ``.items`` (ModelNet / ScanObjectNN / ShapeNet / ShapeSeg; its ``transform`` is not run) or any
         sequence of ``Data``.  Attributes taken: ``pos``, ``norm`` (or ``normal``), ``x``, ``y`` (one per cloud or one per
-        point), ``category`` -- each either on every item or on none, as ``collate`` treats them."""
+        point), ``category`` -- each either on every item or on none, as ``collate`` treats them.  ``fps``: reduce every cloud to
+        that many points with ``geodesic_subsample(fps, seed=fps_seed)`` once it is on the device (``None``: the clouds as they are)."""
         items = list(ds.items if hasattr(ds, "items") and not callable(ds.items) else ds)
         if not items:
             raise ValueError("DeviceDataset: empty dataset")
@@ -157,7 +158,57 @@ class DeviceDataset:
         ptr[1:] = torch.cumsum(torch.tensor(sizes, dtype=torch.int64), 0)
         up = lambda t: None if t is None else t.contiguous().to(device)
         f32 = lambda col: None if col is None else torch.cat(col).float()
-        return cls(up(f32(pos)), up(ptr), sizes, up(f32(norm)), up(f32(x)), up(y_point), up(y_cloud), up(category))
+        store = cls(up(f32(pos)), up(ptr), sizes, up(f32(norm)), up(f32(x)), up(y_point), up(y_cloud), up(category))
+        return store if fps is None else store.geodesic_subsample(fps, seed=fps_seed)
+
+    def geodesic_subsample(self, n_samples, start=None, seed=None, clouds_per_launch=1024):
+        """A new store whose clouds each hold ``n_samples`` geodesic-farthest points of this one's: ``T.GeodesicFPS(n_samples)``
+        (reference: transforms/geodesic_fps.py:14-43) for the whole dataset on the device -- ``geometry.geodesic_fps_batch`` over
+        groups of ``clouds_per_launch`` clouds, then ``pos``, ``norm``, ``x`` and per-point ``y`` gathered by the sample ids.  A
+        cloud of n < n_samples points is tiled as the transform tiles it (``idx[:n].repeat(ceil(n_samples / n))[:n_samples]``).
+        ``start``: the first sample of every cloud (host sequence of ids local to the cloud); otherwise drawn per cloud from
+        ``(seed, dataset index)`` (``geometry.fps.fps_starts``; ``seed=None``: at random), whatever ``clouds_per_launch`` is.
+        A cloud above the device sampler's cap of 16 384 points goes through the host library (``geometry.geodesic_fps``, which
+        derives its start from a seed: an explicit ``start`` for such a cloud raises ``ValueError``) and its ids are uploaded."""
+        from .geometry.fps import FPS_MAX_POINTS, _fps_launches, fps_starts, geodesic_fps
+        m, s, dev = int(n_samples), len(self), self.device
+        if m < 1 or int(clouds_per_launch) < 1:
+            raise ValueError("geodesic_subsample: n_samples >= 1 and clouds_per_launch >= 1")
+        sizes = self.sizes
+        if start is None:
+            starts = fps_starts(sizes, seed)
+        else:
+            starts = np.asarray(start, dtype=np.int64).reshape(-1)
+            if starts.shape != sizes.shape or (starts < 0).any() or (starts >= sizes).any():
+                raise ValueError("geodesic_subsample: `start` must hold one point of every cloud (ids local to the cloud)")
+        ptr_host = np.zeros(s + 1, dtype=np.int64)
+        ptr_host[1:] = np.cumsum(sizes)
+        small = np.flatnonzero(sizes <= FPS_MAX_POINTS)
+        ids = torch.empty((s, m), dtype=torch.int64, device=dev)
+        if small.size == s:
+            ids = _fps_launches(self.pos, ptr_host, m, starts, int(clouds_per_launch)).long()
+        else:
+            if start is not None:
+                raise ValueError(f"geodesic_subsample: a cloud above {FPS_MAX_POINTS} points is sampled by the host library, which "
+                                 "takes a seed, not a start point")
+            if small.size:
+                rows = torch.from_numpy(np.concatenate([np.arange(ptr_host[i], ptr_host[i + 1]) for i in small])).to(dev)
+                ptr_small = np.zeros(small.size + 1, dtype=np.int64)
+                ptr_small[1:] = np.cumsum(sizes[small])
+                ids[torch.from_numpy(small).to(dev)] = _fps_launches(self.pos[rows], ptr_small, m, starts[small],
+                                                                     int(clouds_per_launch)).long()
+            for i in np.flatnonzero(sizes > FPS_MAX_POINTS):
+                pts = self.pos[int(ptr_host[i]):int(ptr_host[i + 1])].cpu().numpy()
+                host_seed = None if seed is None else int(np.random.Generator(np.random.Philox(key=[int(seed), int(i)])).integers(0, 2 ** 31))
+                ids[i] = torch.from_numpy(np.atleast_1d(geodesic_fps(pts, m, seed=host_seed)).astype(np.int64)).to(dev)
+        # the tiling rule of T.GeodesicFPS: column j of a cloud of n < m points is sample j mod n
+        n_dev = torch.from_numpy(np.minimum(sizes, m)).to(dev)
+        cols = torch.arange(m, device=dev)[None, :] % n_dev[:, None]
+        rows = (ids.gather(1, cols) + torch.from_numpy(ptr_host[:-1]).to(dev)[:, None]).reshape(-1)
+        take = lambda t: None if t is None else t[rows].contiguous()
+        ptr = torch.arange(s + 1, dtype=torch.int64, device=dev) * m
+        return DeviceDataset(take(self.pos), ptr, np.full(s, m, dtype=np.int64), take(self.norm), take(self.x), take(self.y_point),
+                             self.y_cloud, self.category)
 
 
 def epoch_permutation(n, seed, epoch, shuffle=True):

@@ -83,7 +83,12 @@ def main():
     ap.add_argument("--device-eval", action="store_true",
                     help="with --device-loader: the per-epoch evaluation on the device (deltaconv_amd.DeviceEvaluator: captured "
                          "forward, metrics in one launch per batch, one synchronise per pass) instead of evaluate() below")
+    ap.add_argument("--device-fps", action="store_true",
+                    help="with --device-loader: GeodesicFPS leaves pre_transform; the oversampled clouds are reduced to num_points on "
+                         "the device, all shapes in a few launches (DeviceDataset.geodesic_subsample) instead of one host call per shape")
     args = ap.parse_args()
+    if args.device_fps and not (args.data is not None and args.device_loader):
+        raise SystemExit("--device-fps samples a device-resident dataset: it needs --data and --device-loader")
     if args.device_eval and not (args.data is not None and args.device_loader):
         raise SystemExit("--device-eval evaluates from a device-resident test set: it needs --data and --device-loader")
 
@@ -103,16 +108,17 @@ def main():
     else:
         import deltaconv_amd.transforms as T
         from deltaconv_amd.datasets import Compose, DataLoader, ModelNet
-        pre = Compose((T.NormalizeScale(), T.SamplePoints(args.num_points * args.sampling_margin, include_normals=True),
-                       T.GeodesicFPS(args.num_points)))
+        pre = (T.NormalizeScale(), T.SamplePoints(args.num_points * args.sampling_margin, include_normals=True))
+        pre = Compose(pre if args.device_fps else pre + (T.GeodesicFPS(args.num_points),))
         aug = Compose((T.RandomScale((4 / 5, 5 / 4)), T.RandomTranslateGlobal(0.1)))
         tr = ModelNet(args.data, None, "40", True, transform=aug, pre_transform=pre)
         te = ModelNet(args.data, None, "40", False, pre_transform=pre)
     if args.data is not None and args.device_loader:
         # the same recipe, drawn and applied on the device; every rank takes its share of one permutation per epoch
-        train = deltaconv.DeviceLoader(deltaconv.DeviceDataset.from_dataset(tr, dev), args.batch_size, shuffle=True,
-                                       drop_last=True, transform=aug, seed=1, rank=rank, world=world)
-        test = deltaconv.DeviceLoader(deltaconv.DeviceDataset.from_dataset(te, dev), args.batch_size)
+        fps = args.num_points if args.device_fps else None      # same start points on every rank: one dataset, many shares
+        train = deltaconv.DeviceLoader(deltaconv.DeviceDataset.from_dataset(tr, dev, fps=fps, fps_seed=1), args.batch_size,
+                                       shuffle=True, drop_last=True, transform=aug, seed=1, rank=rank, world=world)
+        test = deltaconv.DeviceLoader(deltaconv.DeviceDataset.from_dataset(te, dev, fps=fps, fps_seed=1), args.batch_size)
         args.train_batches = len(train)
         if args.device_eval:                 # equal-size clouds (GeodesicFPS to num_points): the full batches replay one graph
             evaluator = deltaconv.DeviceEvaluator(model, test, task="classification")

@@ -31,6 +31,7 @@ extern "C" {
 #define DC_ERR_ARG (-1)
 #define DC_ERR_LAUNCH (-2)
 #define DC_ERR_WORKSPACE (-3)
+#define DC_FPS_MAX_POINTS (16384) /* points per cloud dc_geodesic_fps_batch takes: 8 bytes of LDS per point in one workgroup */
 
 int32_t dc_version(void);
 const char* dc_last_error(void);
@@ -697,6 +698,32 @@ int dc_eval_metrics(const float* logits, int64_t ld_logits, float* votes, const 
                     int64_t Nt, int32_t P, const float* category, int32_t Cc, const int32_t* part_start,
                     const int32_t* part_count, int64_t* pred, double* iou, int32_t* hit, int32_t* cnt, int32_t* ignored,
                     void* stream);
+
+/* ---- geodesic farthest-point sampling of a batch of clouds (csrc/fps.hip, csrc/fps_math.h) ---------------------------------- */
+/* Bytes of workspace dc_geodesic_fps_batch needs for clouds of N points in all (the k = 10 graph: neighbours and fp64 edge
+ * lengths, plus the uploaded offsets and start points).  Reference: deltaconv/transforms/geodesic_fps.py:14-43 and
+ * deltaconv/cpp/sampling.cpp:5-81 (the graph of sampling.cpp:9-31 is the only state between its two stages). */
+size_t dc_geodesic_fps_workspace_bytes(int64_t N);
+/* Replaces the per-shape host call of the reference's data preparation -- deltaconv/transforms/geodesic_fps.py:14-43 over
+ * deltaconv/cpp/sampling.cpp:5-81: the k = 10 nearest-neighbour graph of every cloud (fp64, the point itself left out by index,
+ * ties towards the lower index), then n_samples - 1 rounds of "shortest graph distances from the last sample into a distance
+ * vector that is never reset; the next sample is the FIRST index of its maximum" -- for B clouds in two launches.  The picks are
+ * those of the host library (include/deltaconv_host.h: dc_geodesic_fps) started from the same point: rounds relax edges until
+ * nothing changes instead of running Dijkstra, which reaches the same fp64 distances bit for bit (csrc/fps.hip).
+ *   pos        DEVICE [N,3] contiguous, fp32 (pos_is_f64 = 0) or fp64 (1); fp32 is widened exactly, all arithmetic is fp64
+ *   ptr        HOST [B+1] cloud offsets into pos, ptr[0] = 0, every cloud of 1 .. 16 384 points (DC_FPS_MAX_POINTS: the distance
+ *              vector of a cloud lives in the LDS of one workgroup)
+ *   max_cloud_size  >= the largest cloud, <= 16 384
+ *   start      HOST [B] first sample of every cloud, local to the cloud
+ *   out        DEVICE [B,n_samples] sample ids local to the cloud; n_samples above a cloud's size repeats index 0 once every
+ *              point is taken (the host library does), a disconnected graph takes the first unreached point
+ *   workspace  DEVICE, 8-byte aligned, >= dc_geodesic_fps_workspace_bytes(ptr[B]) bytes (else DC_ERR_WORKSPACE)
+ * A cloud above the cap, an empty cloud, a start outside its cloud, n_samples < 1 or B above 65 535: DC_ERR_ARG with a message
+ * (checked before anything touches the device); B = 0 returns DC_OK.  ptr and start are copied in stream order and may be freed on
+ * return.  No global atomics, no floating-point atomics: the output is a function of the inputs only.  Stream-ordered. */
+int dc_geodesic_fps_batch(const void* pos, int32_t pos_is_f64, const int64_t* ptr, int32_t B, int32_t max_cloud_size,
+                          int32_t n_samples, const int32_t* start, int32_t* out, void* workspace, size_t workspace_bytes,
+                          void* stream);
 
 #ifdef __cplusplus
 }
