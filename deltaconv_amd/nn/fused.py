@@ -142,6 +142,24 @@ def check_bn_rows(bn, rows):
                          f"{bn.num_features}, {int(rows)}]")
 
 
+def bn_mode(bn, rows=None):
+    """The mode of one training / inference pass through `bn` (torch.nn.BatchNorm1d) as the kernels take it:
+    -> (use_batch_stats, momentum, running_mean, running_var, eps).  The ONE place a pass refuses a single-row training batch
+    (`rows` given), advances num_batches_tracked (bump_counter: drops the cached inference coefficients too) and reads the
+    counter back for the cumulative average of `momentum=None`."""
+    if rows is not None:
+        check_bn_rows(bn, rows)
+    use_batch = bn.training or bn.running_mean is None
+    mom = 0.0 if bn.momentum is None else float(bn.momentum)
+    track = bn.training and bn.track_running_stats
+    if track:
+        bump_counter(bn)
+        if bn.momentum is None:
+            mom = 1.0 / float(bn.num_batches_tracked)
+    rm, rv = (bn.running_mean, bn.running_var) if (track or not use_batch) else (None, None)
+    return use_batch, mom, rm, rv, float(bn.eps)
+
+
 def slope_of(act):
     """negative slope of a piecewise-linear activation module, or None if it is something else."""
     if isinstance(act, torch.nn.LeakyReLU):
@@ -151,6 +169,56 @@ def slope_of(act):
     if isinstance(act, torch.nn.Identity):
         return 1.0
     return None
+
+
+def _dgamma_dbeta(c, dev, has_g, has_b):
+    return (torch.empty(c, dtype=torch.float32, device=dev) if has_g else None,
+            torch.empty(c, dtype=torch.float32, device=dev) if has_b else None)
+
+
+def bn_act_backward(dy, lddy, h, coef, gamma, slope, batch_stats, group, has_g=True, has_b=True):
+    """-> (dh, dgamma, dbeta) of y = leaky_slope(batch_norm(h)) on h [R, C] for the incoming dy (row stride lddy).
+    group: the data-parallel group the FORWARD statistics were reduced over, or None -- synchronised statistics take this
+    rank's sums -> all-reduce -> the apply pass with the global means."""
+    r, c = h.shape
+    dev = h.device
+    dh = torch.empty_like(h)
+    dgamma, dbeta = _dgamma_dbeta(c, dev, has_g, has_b)
+    ws, nb = _ws(r, c, dev)
+    if group is not None:
+        stats, _ = _sync_stats(("dc_bn_act_backward_sums", lambda out: (dy, lddy, h, c, r, c, coef[2], coef[3], coef[0],
+                                                                     coef[1], slope, out, ws, nb)), c, r, dev, group)
+        m = torch.empty(2, c, dtype=torch.float32, device=dev)
+        lib.call("dc_sync_means", stats, c, m[0], m[1], dgamma, dbeta)      # global means + this rank's dgamma / dbeta
+        lib.call("dc_bn_act_backward_apply", dy, lddy, h, c, r, c, coef[2], coef[3], coef[0], coef[1], gamma, slope,
+                 int(batch_stats), m[0], m[1], dh, c)
+    else:
+        lib.call("dc_bn_act_backward", dy, lddy, h, c, r, c, coef[2], coef[3], coef[0], coef[1], gamma, slope,
+                 int(batch_stats), dh, c, dgamma, dbeta, ws, nb)
+    return dh, dgamma, dbeta
+
+
+def vn_backward(dout, lddo, h, combine, coef, gamma, batch_stats, group, has_g=True, has_b=True):
+    """-> (dh, dgamma, dbeta) of the vector non-linearity on h ([2n, co], or interleaved (P, Q) [2n, 2co] with `combine`) for
+    the incoming dout (row stride lddo); `group` as in bn_act_backward.  (No BatchNorm at all: gamma = None, batch_stats = 0.)"""
+    ld = h.shape[1]
+    co = ld // 2 if combine else ld
+    n = h.shape[0] // 2
+    dev = h.device
+    dh = torch.empty_like(h)
+    dgamma, dbeta = _dgamma_dbeta(co, dev, has_g, has_b)
+    ws, nb = _ws(n, co, dev)
+    if group is not None:
+        stats, _ = _sync_stats(("dc_vn_backward_sums", lambda out: (dout, lddo, h, ld, combine, n, co, coef[2], coef[3],
+                                                                 coef[0], coef[1], out, ws, nb)), co, n, dev, group)
+        m = torch.empty(2, co, dtype=torch.float32, device=dev)
+        lib.call("dc_sync_means", stats, co, m[0], m[1], dgamma, dbeta)
+        lib.call("dc_vn_backward_apply", dout, lddo, h, ld, combine, n, co, coef[2], coef[3], coef[0], coef[1], gamma, 1,
+                 m[0], m[1], dh, ld)
+    else:
+        lib.call("dc_vn_backward", dout, lddo, h, ld, combine, n, co, coef[2], coef[3], coef[0], coef[1], gamma,
+                 int(batch_stats), dh, ld, dgamma, dbeta, ws, nb)
+    return dh, dgamma, dbeta
 
 
 class _BNAct(torch.autograd.Function):
@@ -186,36 +254,15 @@ class _BNAct(torch.autograd.Function):
         h, coef, gamma = ctx.saved_tensors
         training, slope, has_g, has_b, has_res = ctx.cfg
         dy = _c(dy)
-        r, c = h.shape
-        dh = torch.empty_like(h)
-        dgamma = torch.empty(c, dtype=torch.float32, device=h.device) if has_g else None
-        dbeta = torch.empty(c, dtype=torch.float32, device=h.device) if has_b else None
-        ws, nb = _ws(r, c, h.device)
-        if ctx.group is not None:
-            stats, _ = _sync_stats(("dc_bn_act_backward_sums", lambda out: (dy, c, h, c, r, c, coef[2], coef[3], coef[0],
-                                                                         coef[1], slope, out, ws, nb)), c, r, h.device, ctx.group)
-            m = torch.empty(2, c, dtype=torch.float32, device=h.device)
-            lib.call("dc_sync_means", stats, c, m[0], m[1], dgamma, dbeta)      # global means + this rank's dgamma / dbeta
-            lib.call("dc_bn_act_backward_apply", dy, c, h, c, r, c, coef[2], coef[3], coef[0], coef[1], gamma, slope,
-                     int(training), m[0], m[1], dh, c)
-        else:
-            lib.call("dc_bn_act_backward", dy, c, h, c, r, c, coef[2], coef[3], coef[0], coef[1], gamma, slope,
-                     int(training), dh, c, dgamma, dbeta, ws, nb)
+        dh, dgamma, dbeta = bn_act_backward(dy, h.shape[1], h, coef, gamma, slope, training, ctx.group, has_g, has_b)
         return dh, dgamma, dbeta, None, None, None, None, None, None, (dy if has_res else None)
 
 
 def bn_act(h, bn, slope, residual=None):
     """bn: torch.nn.BatchNorm1d holding the parameters / running statistics."""
     require_gpu()
-    check_bn_rows(bn, h.shape[0])
-    use_batch = bn.training or bn.running_mean is None
-    mom = 0.0 if bn.momentum is None else float(bn.momentum)
-    rm, rv = (bn.running_mean, bn.running_var) if (bn.training and bn.track_running_stats) or not use_batch else (None, None)
-    if bn.training and bn.track_running_stats:
-        bump_counter(bn)
-        if bn.momentum is None:
-            mom = 1.0 / float(bn.num_batches_tracked)
-    return _BNAct.apply(h, bn.weight, bn.bias, rm, rv, use_batch, mom, float(bn.eps), float(slope), residual)
+    use_batch, mom, rm, rv, eps = bn_mode(bn, h.shape[0])
+    return _BNAct.apply(h, bn.weight, bn.bias, rm, rv, use_batch, mom, eps, float(slope), residual)
 
 
 class _VectorNonLin(torch.autograd.Function):
@@ -256,24 +303,8 @@ class _VectorNonLin(torch.autograd.Function):
         inp, coef, gamma = ctx.saved_tensors
         combine, mode, has_g, has_b = ctx.cfg
         dout = _c(dout)
-        ld = inp.shape[1]
-        co = ld // 2 if combine else ld
-        n = inp.shape[0] // 2
-        dev = inp.device
-        din = torch.empty_like(inp)
-        dgamma = torch.empty(co, dtype=torch.float32, device=dev) if has_g else None
-        dbeta = torch.empty(co, dtype=torch.float32, device=dev) if has_b else None
-        ws, nb = _ws(n, co, dev)
-        if ctx.group is not None:
-            stats, _ = _sync_stats(("dc_vn_backward_sums", lambda out: (dout, co, inp, ld, combine, n, co, coef[2], coef[3],
-                                                                     coef[0], coef[1], out, ws, nb)), co, n, dev, ctx.group)
-            m = torch.empty(2, co, dtype=torch.float32, device=dev)
-            lib.call("dc_sync_means", stats, co, m[0], m[1], dgamma, dbeta)
-            lib.call("dc_vn_backward_apply", dout, co, inp, ld, combine, n, co, coef[2], coef[3], coef[0], coef[1], gamma,
-                     1, m[0], m[1], din, ld)
-        else:
-            lib.call("dc_vn_backward", dout, co, inp, ld, combine, n, co, coef[2], coef[3], coef[0], coef[1],
-                     gamma if mode else None, int(mode == 2), din, ld, dgamma, dbeta, ws, nb)
+        din, dgamma, dbeta = vn_backward(dout, dout.shape[1], inp, combine, coef, gamma if mode else None, mode == 2, ctx.group,
+                                         has_g, has_b)
         return din, None, dgamma, dbeta, None, None, None, None, None
 
 
@@ -283,16 +314,28 @@ def vector_nonlin(inp, combine, vn):
     if vn.batchnorm is None:
         return _VectorNonLin.apply(inp, combine, None, vn.bias, None, None, 0, 0.0, 0.0)
     bn = vn.batchnorm.bn
-    check_bn_rows(bn, inp.shape[0] // 2)
-    use_batch = bn.training or bn.running_mean is None
-    mom = 0.0 if bn.momentum is None else float(bn.momentum)
-    track = bn.training and bn.track_running_stats
-    if track:
-        bump_counter(bn)
-        if bn.momentum is None:
-            mom = 1.0 / float(bn.num_batches_tracked)
-    rm, rv = (bn.running_mean, bn.running_var) if (track or not use_batch) else (None, None)
-    return _VectorNonLin.apply(inp, combine, bn.weight, bn.bias, rm, rv, 2 if use_batch else 1, mom, float(bn.eps))
+    use_batch, mom, rm, rv, eps = bn_mode(bn, inp.shape[0] // 2)
+    return _VectorNonLin.apply(inp, combine, bn.weight, bn.bias, rm, rv, 2 if use_batch else 1, mom, eps)
+
+
+def edge_gather_stats(y, graph, mode, gamma, beta, coef=None):
+    """First pass of the centralised max aggregation over y [n, C] (row-major, dense): per point the extremes of y_j over its
+    k-list, their slots and the first moment, together with the BatchNorm statistics of y_j - y_i over all edges.
+    mode = bn_mode(...) of that BatchNorm.  -> (stat [3, n, C] = amax | amin | s1pt, args uint8 [2, n, C], coef [4, C]); with
+    batch statistics off, coef is the layer's inference map (eval_coeffs; `coef`: already fetched by the caller)."""
+    use, mom, rm, rv, eps = mode
+    n, c = y.shape
+    dev = y.device
+    stat = torch.empty(3, n, c, dtype=torch.float32, device=dev)
+    args = torch.empty(2, n, c, dtype=torch.uint8, device=dev)
+    if coef is None and use:
+        coef = torch.empty(4, c, dtype=torch.float32, device=dev)      # mean, invstd, scale, shift
+    ws, nb = _ws(n, c, dev)
+    if coef is None:
+        coef = eval_coeffs(gamma, beta, rm, rv, eps, c)
+    lib.call("dc_edge_gather_stats", y, c, graph.nbr, n, graph.k, c, int(use), gamma, beta, eps, mom, rm if use else None,
+             rv if use else None, stat[0], stat[1], args[0], args[1], stat[2], coef[0], coef[1], coef[2], coef[3], ws, nb)
+    return stat, args, coef
 
 
 class _EdgeMaxBN(torch.autograd.Function):
@@ -300,24 +343,14 @@ class _EdgeMaxBN(torch.autograd.Function):
     without materialising any [E,C] tensor (csrc/edge_math.h)."""
 
     @staticmethod
-    def forward(ctx, y, graph, gamma, beta, rm, rv, use_batch_stats, momentum, eps, slope):
+    def forward(ctx, y, graph, gamma, beta, mode, slope):
         y = _c(y)
         n, c = y.shape
-        k, dev = graph.k, y.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        stat = torch.empty(3, n, c, **f32)                   # amax, amin, s1pt
-        args = torch.empty(2, n, c, dtype=torch.uint8, device=dev)
-        coef = torch.empty(4, c, **f32)                      # mean, invstd, scale, shift
-        ws, nb = _ws(n, c, dev)
-        if not use_batch_stats:
-            coef = eval_coeffs(gamma, beta, rm, rv, eps, c)
-        lib.call("dc_edge_gather_stats", y, c, graph.nbr, n, k, c, int(use_batch_stats), gamma, beta, eps, momentum,
-                 rm if use_batch_stats else None, rv if use_batch_stats else None, stat[0], stat[1], args[0], args[1],
-                 stat[2], coef[0], coef[1], coef[2], coef[3], ws, nb)
-        out = torch.empty(n, c, **f32)
+        stat, args, coef = edge_gather_stats(y, graph, mode, gamma, beta)
+        out = torch.empty(n, c, dtype=torch.float32, device=y.device)
         lib.call("dc_edge_max_apply", stat[0], stat[1], args[0], args[1], n, c, coef[2], coef[3], slope, out, c, None)
         ctx.save_for_backward(y, stat, args, coef)
-        ctx.graph, ctx.cfg = graph, (use_batch_stats, slope, gamma is not None, beta is not None)
+        ctx.graph, ctx.cfg = graph, (mode[0], slope, gamma is not None, beta is not None)
         return out
 
     @staticmethod
@@ -331,26 +364,17 @@ class _EdgeMaxBN(torch.autograd.Function):
         tptr, tedge = g.csc()
         dzs = torch.empty(n, c, dtype=torch.float32, device=dev)
         dy = torch.empty(n, c, dtype=torch.float32, device=dev)
-        dgamma = torch.empty(c, dtype=torch.float32, device=dev) if has_g else None
-        dbeta = torch.empty(c, dtype=torch.float32, device=dev) if has_b else None
+        dgamma, dbeta = _dgamma_dbeta(c, dev, has_g, has_b)
         ws, nb = _ws(n, c, dev)
         lib.call("dc_edge_max_backward", dout, c, y, c, tptr, tedge, n, g.k, c, stat[0], stat[1], args[0], args[1],
                  stat[2], coef[2], coef[3], coef[0], coef[1], slope, int(training), dzs, dy, c, dgamma, dbeta, ws, nb)
-        return dy, None, dgamma, dbeta, None, None, None, None, None, None
+        return dy, None, dgamma, dbeta, None, None
 
 
 def edge_max_bn(y, graph, bn, slope):
     """bn: torch.nn.BatchNorm1d of the (single) s_mlp_max block; y = Linear(x)."""
     require_gpu()
-    use_batch = bn.training or bn.running_mean is None
-    mom = 0.0 if bn.momentum is None else float(bn.momentum)
-    track = bn.training and bn.track_running_stats
-    if track:
-        bump_counter(bn)
-        if bn.momentum is None:
-            mom = 1.0 / float(bn.num_batches_tracked)
-    rm, rv = (bn.running_mean, bn.running_var) if (track or not use_batch) else (None, None)
-    return _EdgeMaxBN.apply(y, graph, bn.weight, bn.bias, rm, rv, use_batch, mom, float(bn.eps), float(slope))
+    return _EdgeMaxBN.apply(y, graph, bn.weight, bn.bias, bn_mode(bn), float(slope))     # (no row check: statistics over edges)
 
 
 class _EdgeDiff(torch.autograd.Function):
@@ -450,13 +474,7 @@ class _EdgeMLP2(torch.autograd.Function):
                          coef1[1], coef1[2], coef1[3], ws2, nb2)
         else:
             z = mm_nt(x, W1)                                       # [n, 64]: W1 (x_j - x_i) = z_j - z_i
-            stat = torch.empty(3, n, c, **f32)                     # amax, amin (unused here), s1pt
-            args = torch.empty(2, n, c, dtype=torch.uint8, device=dev)
-            ws, nb = _ws(n, c, dev)
-            lib.call("dc_edge_gather_stats", z, c, graph.nbr, n, k, c, int(use1), g1, b1, eps1, mom1, rm1 if use1 else None,
-                     rv1 if use1 else None, stat[0], stat[1], args[0], args[1], stat[2], coef1[0], coef1[1], coef1[2], coef1[3],
-                     ws, nb)
-            s1 = stat[2]
+            s1 = edge_gather_stats(z, graph, mode1, g1, b1, coef=coef1)[0][2]      # s1pt (amax, amin unused here)
         coef2 = torch.empty(4, c, **f32) if use2 else eval_coeffs(g2, b2, rm2, rv2, eps2, c)
         ysel = torch.empty(n, c, **f32)
         arg = torch.empty(n, c, dtype=torch.uint8, device=dev)
@@ -486,22 +504,9 @@ class _EdgeMLP2(torch.autograd.Function):
         ws = torch.empty((nb + 7) // 8, dtype=torch.float64, device=dev)
         lib.call("dc_edge2_backward", dout, c, z, x, x.stride(0), x.shape[1], W1, g.nbr, tptr, tedge, n, k, W2, coef1, coef2, g2,
                  slope1, slope2, int(use1), int(use2), ysel, arg, s1, dz, c, dW2, dg1, db1, dg2, db2, ws, nb)
-        dW1 = gemm_tn(dz, x if x.stride(1) == 1 else x.contiguous()) if ctx.needs_input_grad[2] else None
-        dx = mm_nn(dz, W1) if ctx.needs_input_grad[0] else None
+        dW1, dx = linear_grads(dz, x, W1, need_dx=ctx.needs_input_grad[0], need_dw=ctx.needs_input_grad[2])
         return (dx, None, dW1, dg1 if hg1 else None, db1 if hb1 else None, dW2, dg2 if hg2 else None, db2 if hb2 else None,
                 None, None, None, None)
-
-
-def _bn_mode_of(bn):
-    use_batch = bn.training or bn.running_mean is None
-    mom = 0.0 if bn.momentum is None else float(bn.momentum)
-    track = bn.training and bn.track_running_stats
-    if track:
-        bump_counter(bn)
-        if bn.momentum is None:
-            mom = 1.0 / float(bn.num_batches_tracked)
-    rm, rv = (bn.running_mean, bn.running_var) if (track or not use_batch) else (None, None)
-    return use_batch, mom, rm, rv, float(bn.eps)
 
 
 def edge_mlp2_ok(x, lin1, bn1, lin2, bn2, slope1, slope2):
@@ -514,8 +519,7 @@ def edge_mlp2_ok(x, lin1, bn1, lin2, bn2, slope1, slope2):
 def edge_mlp2(x, graph, lin1, bn1, slope1, lin2, bn2, slope2):
     """bn1 / bn2: torch.nn.BatchNorm1d of the two blocks; returns (x_max [n, 64], selected slots uint8 [n, 64])."""
     require_gpu()
-    check_bn_rows(bn1, graph.n * graph.k)
-    m1, m2 = _bn_mode_of(bn1), _bn_mode_of(bn2)
+    m1, m2 = bn_mode(bn1, graph.n * graph.k), bn_mode(bn2)
     return _EdgeMLP2.apply(_c(x), graph, lin1.weight, bn1.weight, bn1.bias, _c(lin2.weight), bn2.weight, bn2.bias, m1, m2,
                            float(slope1), float(slope2))
 
@@ -583,13 +587,8 @@ def presplit_begin():
                     # cross-device pointers
                     continue
                 order.append(key_)
-                n, k = e["n"], e["k"]
-                for need in ("fwd", "bwd"):
-                    if e["want_" + need] and e[need] is None:
-                        e[need] = torch.empty(3 * n * k, dtype=torch.int16, device=e["dev"])
-                rows.append([e["ptr"], e["fwd"].data_ptr() if e["fwd"] is not None else 0,
-                             e["bwd"].data_ptr() if e["bwd"] is not None else 0, n, k, k])
-                total += (n * k + 1023) // 1024
+                rows.append(_plane_row(e))
+                total += (e["n"] * e["k"] + 1023) // 1024
                 starts.append(total)
             if not rows:
                 _PL.update(table=None, chunks=None, n_chunks=0, dirty=False)
@@ -621,14 +620,20 @@ def presplit_begin():
             e["epoch"], e["version"] = _PL["epoch"], (w._version if w is not None else -1)
 
 
-def _split_one(e, base):
-    """Cut ONE weight now (its first use, or a use after it changed without a presplit_begin): a one-record table."""
+def _plane_row(e):
+    """The record of one weight in a dc_presplit_weights table: (source, forward planes or 0, transposed planes or 0, n, k, ld);
+    the plane buffers the entry wants and does not have yet are allocated here."""
     n, k = e["n"], e["k"]
     for need in ("fwd", "bwd"):
         if e["want_" + need] and e[need] is None:
             e[need] = torch.empty(3 * n * k, dtype=torch.int16, device=e["dev"])
-    row = [[e["ptr"], e["fwd"].data_ptr() if e["fwd"] is not None else 0, e["bwd"].data_ptr() if e["bwd"] is not None else 0, n, k, k]]
-    chunks = (n * k + 1023) // 1024
+    return [e["ptr"], e["fwd"].data_ptr() if e["fwd"] is not None else 0, e["bwd"].data_ptr() if e["bwd"] is not None else 0, n, k, k]
+
+
+def _split_one(e, base):
+    """Cut ONE weight now (its first use, or a use after it changed without a presplit_begin): a one-record table."""
+    row = [_plane_row(e)]
+    chunks = (e["n"] * e["k"] + 1023) // 1024
     lib.call("dc_presplit_weights", torch.tensor(row, dtype=torch.int64).to(e["dev"]),
              torch.tensor([0, chunks], dtype=torch.int32).to(e["dev"]), 1, chunks)
     e["epoch"], e["version"] = _PL["epoch"], base._version
@@ -848,12 +853,12 @@ def mm_nn(dy, w, out=None, accumulate=False):
     return out
 
 
-def linear_grads(dh, x, w, dx_out=None, accumulate=False):
-    """Both gradients of y = x w^T for the incoming dh [R, N]: -> (dW [N, K], dX [R, K]); dX lands in `dx_out`
-    (+= when accumulate) if given."""
-    dh, w = _rowmajor(dh), _rowmajor(w)
-    xx = x if x.stride(1) == 1 else x.contiguous()
-    return gemm_tn(dh, xx), mm_nn(dh, w, out=dx_out, accumulate=accumulate)
+def linear_grads(dh, x, w, dx_out=None, accumulate=False, need_dx=True, need_dw=True):
+    """The gradients of y = x w^T for the incoming dh [R, N]: -> (dW [N, K], dX [R, K]), None for one that is not needed
+    (ctx.needs_input_grad of the caller); dX lands in `dx_out` (+= when accumulate) if given."""
+    dh = _rowmajor(dh)
+    dw = gemm_tn(dh, x if x.stride(1) == 1 else x.contiguous()) if need_dw else None
+    return dw, (mm_nn(dh, w, out=dx_out, accumulate=accumulate) if need_dx else None)
 
 
 def linear_stats(x, w, bn, gamma, beta, vn=0, defer_final=False):
@@ -868,18 +873,10 @@ def linear_stats(x, w, bn, gamma, beta, vn=0, defer_final=False):
     c = n // 2 if vn == 2 else n
     rows = m // 2 if vn else m
     dev = x.device
-    check_bn_rows(bn, rows)
-    use_batch = bn.training or bn.running_mean is None
-    mom = 0.0 if bn.momentum is None else float(bn.momentum)
-    track = bn.training and bn.track_running_stats
-    if track:
-        bump_counter(bn)
-        if bn.momentum is None:
-            mom = 1.0 / float(bn.num_batches_tracked)
-    rm, rv = (bn.running_mean, bn.running_var) if (track or not use_batch) else (None, None)
+    _require_fp32_gpu("linear_stats", x, w)        # before bn_mode: a refused call leaves the layer's counter and caches alone
+    use_batch, mom, rm, rv, eps = bn_mode(bn, rows)
     coef = torch.empty(4, c, dtype=torch.float32, device=dev)
     h = torch.empty(m, n, dtype=torch.float32, device=dev)
-    _require_fp32_gpu("linear_stats", x, w)
     group = sync_group() if use_batch else None
     if group is not None:
         # statistics of the GLOBAL batch (deltaconv_amd/dp.py): the same GEMM epilogue, cut at the reduction -- this rank's fp64
@@ -895,7 +892,7 @@ def linear_stats(x, w, bn, gamma, beta, vn=0, defer_final=False):
         else:
             lib.call("dc_linear_bn_sums_forward", x, x.stride(0), w, w.stride(0), m, n, k, h, n, sums, 0, ws, nb)
         dp.all_reduce_stats(sums[0], group)
-        lib.call("dc_bn_coeffs_from_sums", sums[0], 0, c, gamma, beta, float(bn.eps), mom, rm, rv, coef[0], coef[1], coef[2], coef[3])
+        lib.call("dc_bn_coeffs_from_sums", sums[0], 0, c, gamma, beta, eps, mom, rm, rv, coef[0], coef[1], coef[2], coef[3])
         return h, coef, BatchStats(group)
     if use_batch:
         nb = lib.raw("dc_linear_stats_workspace_bytes")(m, n, k, 0)
@@ -903,15 +900,15 @@ def linear_stats(x, w, bn, gamma, beta, vn=0, defer_final=False):
         _hint_planes(w, False)
         if vn:
             lib.call("dc_linear_vn_stats_forward", x, x.stride(0), w, w.stride(0), rows, c, k, h, n, int(vn == 2), gamma,
-                     beta, float(bn.eps), mom, rm, rv, coef[0], coef[1], coef[2], coef[3], 0, ws, nb)
+                     beta, eps, mom, rm, rv, coef[0], coef[1], coef[2], coef[3], 0, ws, nb)
         else:
             if defer_final:
                 _defer_final(ws)           # (inside fin_batch(): coef is valid when that block exits)
             lib.call("dc_linear_bn_stats_forward", x, x.stride(0), w, w.stride(0), m, n, k, h, n, gamma, beta,
-                     float(bn.eps), mom, rm, rv, coef[0], coef[1], coef[2], coef[3], 0, ws, nb)
+                     eps, mom, rm, rv, coef[0], coef[1], coef[2], coef[3], 0, ws, nb)
         return h, coef, BatchStats(None)
     mm_nt(x, w, out=h)                 # inference: coefficients from the running statistics
-    return h, eval_coeffs(gamma, beta, rm, rv, float(bn.eps), c), False
+    return h, eval_coeffs(gamma, beta, rm, rv, eps, c), False
 
 
 FUSE_BN_BWD = True     # A/B switch: BatchNorm/activation backward folded into the consuming GEMMs (no dh tensor)
@@ -987,28 +984,17 @@ def bn_block_backward(dy, lddy, inp, h, coef, use_batch, gamma, slope, W, want_d
     state = bn_block_reduce(dy, lddy, inp, h, coef, use_batch, gamma, slope, W)
     if state is not None:
         return bn_block_products(state, want_dinp, dinp_out, accumulate)
-    r, c = h.shape
-    k = W.shape[1]
-    dev = h.device
-    group = group_of(use_batch)
-    if group is not None:              # same shapes on every rank: every rank raises here, before any collective
-        raise NotImplementedError(f"synchronised BatchNorm backward of a fused block with {c} x {k} > {OWN_TN_MAX_OUTPUTS} "
-                                  "weight entries (the un-fused form has no split reduction)")
-    dg = torch.empty(c, dtype=torch.float32, device=dev)
-    db = torch.empty(c, dtype=torch.float32, device=dev)
-    ws, nb = _ws(r, c, dev)
-    inp = _rowmajor(inp)
-    dh = torch.empty_like(h)
-    lib.call("dc_bn_act_backward", dy, lddy, h, c, r, c, coef[2], coef[3], coef[0], coef[1], gamma, slope, int(use_batch),
-             dh, c, dg, db, ws, nb)
-    dW = gemm_tn(dh, inp)
-    dinp = mm_nn(dh, W, out=dinp_out, accumulate=accumulate) if want_dinp else None
+    if group_of(use_batch) is not None:    # same shapes on every rank: every rank raises here, before any collective
+        raise NotImplementedError(f"synchronised BatchNorm backward of a fused block with {h.shape[1]} x {W.shape[1]} > "
+                                  f"{OWN_TN_MAX_OUTPUTS} weight entries (the un-fused form has no split reduction)")
+    dh, dg, db = bn_act_backward(dy, lddy, h, coef, gamma, slope, use_batch, None)
+    dW, dinp = linear_grads(dh, _rowmajor(inp), W, dinp_out, accumulate, need_dx=want_dinp)
     return dW, dg, db, dinp
 
 
 class _Linear(torch.autograd.Function):
     """y = x W^T (+ b) on 2-D row-major x: forward and input gradient through csrc/gemm.hip, the weight gradient
-    dW = dY^T X through `gemm_tn` (own fp32-MFMA kernels; small / per-cloud problems stay with the library)."""
+    dW = dY^T X through `gemm_tn` (csrc/gemm_tn.hip, whatever the shape).  No library product: see _require_fp32_gpu."""
 
     @staticmethod
     def forward(ctx, x, w, b):
@@ -1024,11 +1010,7 @@ class _Linear(torch.autograd.Function):
         x, w = ctx.saved_tensors
         if dy.stride(1) != 1:
             dy = dy.contiguous()
-        if ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:
-            dw, dx = linear_grads(dy, x, w)
-        else:
-            dx = mm_nn(dy, w) if ctx.needs_input_grad[0] else None
-            dw = gemm_tn(dy, x if x.stride(1) == 1 else x.contiguous()) if ctx.needs_input_grad[1] else None
+        dw, dx = linear_grads(dy, x, w, need_dx=ctx.needs_input_grad[0], need_dw=ctx.needs_input_grad[1])
         db = dy.sum(0) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
         return dx, dw, db
 
@@ -1077,16 +1059,14 @@ class _LinearBiasAct(torch.autograd.Function):
         # (slope 1: act' = 1 whatever h is -- dy itself stands in for the pre-activation that was not kept)
         lib.call("dc_bn_act_backward", dy, c, h if h is not None else dy, c, r, c, one, b, zero, one, None, slope, 0, dh, c,
                  None, db, ws, nb)
-        if ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:
-            dw, dx = linear_grads(dh, x, w)
-        else:
-            dx = mm_nn(dh, w) if ctx.needs_input_grad[0] else None
-            dw = gemm_tn(dh, x if x.stride(1) == 1 else x.contiguous()) if ctx.needs_input_grad[1] else None
+        dw, dx = linear_grads(dh, x, w, need_dx=ctx.needs_input_grad[0], need_dw=ctx.needs_input_grad[1])
         return dx, dw, (db if ctx.needs_input_grad[2] else None), None
 
 
 def linear_bias_act(x, w, b, slope=1.0):
-    """leaky_slope(x W^T + b) -- own kernels for 2-D fp32 GPU inputs with a bias, else torch."""
+    """leaky_slope(x W^T + b): product + one bias / activation pass for 2-D fp32 device tensors with an fp32 bias on more rows
+    than a row block takes; otherwise `linear` (the same hand-written products, or the row-block kernel; it raises for anything
+    but 2-D fp32 device tensors -- no torch product) with ATen's leaky_relu behind it."""
     if (USE_BIAS_ACT and b is not None and x.dim() == 2 and x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32
             and b.dtype == torch.float32 and slope >= 0 and not _rowblock_ok(x, w)):
         return _LinearBiasAct.apply(_c(x), w, b, float(slope))
@@ -1096,7 +1076,7 @@ def linear_bias_act(x, w, b, slope=1.0):
 
 # ---- blocks on a handful of rows (classification head: one row per cloud): csrc/rowblock.hip ------------------------
 ROWBLOCK_MAX_ROWS = 64
-USE_ROWBLOCK = True        # A/B switch: False = the composed path (library GEMM + statistics + finaliser + activation)
+USE_ROWBLOCK = True        # A/B switch: False = the many-row path (csrc/gemm.hip product with statistics epilogue + activation kernel)
 
 
 def _rows16(t):
@@ -1130,15 +1110,7 @@ class _RowBlock(torch.autograd.Function):
         x, w = _rowmajor(x), _rowmajor(w)
         m, k = x.shape
         n = w.shape[0]
-        check_bn_rows(bn, m)
-        use_batch = bn.training or bn.running_mean is None
-        mom = 0.0 if bn.momentum is None else float(bn.momentum)
-        track = bn.training and bn.track_running_stats
-        if track:
-            bump_counter(bn)
-            if bn.momentum is None:
-                mom = 1.0 / float(bn.num_batches_tracked)
-        rm, rv = (bn.running_mean, bn.running_var) if (track or not use_batch) else (None, None)
+        use_batch, mom, rm, rv, eps = bn_mode(bn, m)
         dev = x.device
         h = torch.empty(m, n, dtype=torch.float32, device=dev)
         y = torch.empty(m, n, dtype=torch.float32, device=dev)
@@ -1146,11 +1118,11 @@ class _RowBlock(torch.autograd.Function):
         mask = None
         if drop is not None:
             mask = torch.empty(m, n, dtype=torch.uint8, device=dev)
-            lib.call("dc_rowblock_forward_dropout", x, x.stride(0), w, w.stride(0), m, n, k, gamma, beta, float(bn.eps), mom, rm,
+            lib.call("dc_rowblock_forward_dropout", x, x.stride(0), w, w.stride(0), m, n, k, gamma, beta, eps, mom, rm,
                      rv, 1 if use_batch else 2, slope, h, n, coef, y, n, float(drop[0]), _seed32(), bn.num_batches_tracked,
                      int(drop[1]), mask)
         else:
-            lib.call("dc_rowblock_forward", x, x.stride(0), w, w.stride(0), None, m, n, k, gamma, beta, float(bn.eps), mom, rm,
+            lib.call("dc_rowblock_forward", x, x.stride(0), w, w.stride(0), None, m, n, k, gamma, beta, eps, mom, rm,
                      rv, 1 if use_batch else 2, slope, h, n, coef, y, n)
         ctx.save_for_backward(x, w, h, coef, gamma, mask)
         ctx.cfg = (use_batch, slope, gamma is not None, beta is not None, None if drop is None else float(drop[0]))
@@ -1346,6 +1318,29 @@ def linear_bn_act(x, lin, bn, slope, residual=None, dropout=None):
     return bn_act(linear(x, lin.weight, lin.bias), bn, slope, residual)
 
 
+def _pool_forward(h, coef, slope, num_clouds, n_per, with_mean):
+    """-> (pooled [B, (2)C] = [max | mean] over each cloud of leaky_slope(coef[2] h + coef[3]), arg int32 [B, C] = the row of each max)."""
+    c = h.shape[1]
+    width = 2 * c if with_mean else c
+    pooled = torch.empty(num_clouds, width, dtype=torch.float32, device=h.device)
+    arg = torch.empty(num_clouds, c, dtype=torch.int32, device=h.device)
+    lib.call("dc_bn_act_pool", h, c, num_clouds, n_per, c, coef[2], coef[3], slope, int(with_mean), pooled, width, arg)
+    return pooled, arg
+
+
+def _pool_backward(dpooled, arg, h, coef, gamma, cfg):
+    """-> (dh, dgamma, dbeta) through the pooling, the activation and the BatchNorm; cfg = ctx.cfg of the two pooling nodes."""
+    training, slope, num_clouds, n_per, with_mean, has_g, has_b = cfg
+    dpooled = _c(dpooled)
+    r, c = h.shape
+    dh = torch.empty_like(h)
+    dgamma, dbeta = _dgamma_dbeta(c, h.device, has_g, has_b)
+    ws, nb = _ws(r, c, h.device)
+    lib.call("dc_bn_act_pool_backward", dpooled, dpooled.shape[1], arg, h, c, num_clouds, n_per, c, coef[2], coef[3],
+             coef[0], coef[1], gamma, slope, int(with_mean), int(training), dh, c, dgamma, dbeta, ws, nb)
+    return dh, dgamma, dbeta
+
+
 class _LinearBNActPool(torch.autograd.Function):
     """pooled[B, (2)C] = [max | mean] over each cloud of leaky(batch_norm(x W^T)): the embedding MLP in front of the
     global pooling (models/deltanet_classification.py:42-49, deltanet_segmentation.py:58-61).  Statistics from the
@@ -1355,13 +1350,7 @@ class _LinearBNActPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, gamma, beta, bn, slope, num_clouds, n_per, with_mean):
         h, coef, use_batch = linear_stats(x, w, bn, gamma, beta)
-        r, c = h.shape
-        dev = h.device
-        width = 2 * c if with_mean else c
-        pooled = torch.empty(num_clouds, width, dtype=torch.float32, device=dev)
-        arg = torch.empty(num_clouds, c, dtype=torch.int32, device=dev)
-        lib.call("dc_bn_act_pool", h, c, num_clouds, n_per, c, coef[2], coef[3], slope, int(with_mean), pooled, width,
-                 arg)
+        pooled, arg = _pool_forward(h, coef, slope, num_clouds, n_per, with_mean)
         ctx.save_for_backward(x, w, h, coef, gamma, arg)
         ctx.cfg = (use_batch, slope, num_clouds, n_per, with_mean, gamma is not None, beta is not None)
         return pooled
@@ -1369,21 +1358,8 @@ class _LinearBNActPool(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dpooled):
         x, w, h, coef, gamma, arg = ctx.saved_tensors
-        training, slope, num_clouds, n_per, with_mean, has_g, has_b = ctx.cfg
-        dpooled = _c(dpooled)
-        r, c = h.shape
-        dev = h.device
-        dh = torch.empty_like(h)
-        dgamma = torch.empty(c, dtype=torch.float32, device=dev) if has_g else None
-        dbeta = torch.empty(c, dtype=torch.float32, device=dev) if has_b else None
-        ws, nb = _ws(r, c, dev)
-        lib.call("dc_bn_act_pool_backward", dpooled, dpooled.shape[1], arg, h, c, num_clouds, n_per, c, coef[2], coef[3],
-                 coef[0], coef[1], gamma, slope, int(with_mean), int(training), dh, c, dgamma, dbeta, ws, nb)
-        if ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:
-            dw, dx = linear_grads(dh, x, w)
-        else:
-            dw = gemm_tn(dh, x if x.stride(1) == 1 else x.contiguous()) if ctx.needs_input_grad[1] else None
-            dx = mm_nn(dh, w) if ctx.needs_input_grad[0] else None
+        dh, dgamma, dbeta = _pool_backward(dpooled, arg, h, coef, gamma, ctx.cfg)
+        dw, dx = linear_grads(dh, x, w, need_dx=ctx.needs_input_grad[0], need_dw=ctx.needs_input_grad[1])
         return dx, dw, dgamma, dbeta, None, None, None, None, None
 
 
@@ -1408,11 +1384,7 @@ class _BNActPool(torch.autograd.Function):
                      coef[3], ws, nb)
         else:
             coef = eval_coeffs(gamma, beta, rm, rv, eps, c)
-        width = 2 * c if with_mean else c
-        pooled = torch.empty(num_clouds, width, dtype=torch.float32, device=dev)
-        arg = torch.empty(num_clouds, c, dtype=torch.int32, device=dev)
-        lib.call("dc_bn_act_pool", h, c, num_clouds, n_per, c, coef[2], coef[3], slope, int(with_mean), pooled, width,
-                 arg)
+        pooled, arg = _pool_forward(h, coef, slope, num_clouds, n_per, with_mean)
         ctx.save_for_backward(h, coef, gamma, arg)
         ctx.cfg = (use_batch_stats, slope, num_clouds, n_per, with_mean, gamma is not None, beta is not None)
         return pooled
@@ -1420,29 +1392,11 @@ class _BNActPool(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dpooled):
         h, coef, gamma, arg = ctx.saved_tensors
-        training, slope, num_clouds, n_per, with_mean, has_g, has_b = ctx.cfg
-        dpooled = _c(dpooled)
-        r, c = h.shape
-        dev = h.device
-        dh = torch.empty_like(h)
-        dgamma = torch.empty(c, dtype=torch.float32, device=dev) if has_g else None
-        dbeta = torch.empty(c, dtype=torch.float32, device=dev) if has_b else None
-        ws, nb = _ws(r, c, dev)
-        lib.call("dc_bn_act_pool_backward", dpooled, dpooled.shape[1], arg, h, c, num_clouds, n_per, c, coef[2], coef[3],
-                 coef[0], coef[1], gamma, slope, int(with_mean), int(training), dh, c, dgamma, dbeta, ws, nb)
+        dh, dgamma, dbeta = _pool_backward(dpooled, arg, h, coef, gamma, ctx.cfg)
         return dh, dgamma, dbeta, None, None, None, None, None, None, None, None, None
 
 
 def bn_act_pool(h, bn, slope, num_clouds, n_per, with_mean):
     require_gpu()
-    check_bn_rows(bn, h.shape[0])
-    use_batch = bn.training or bn.running_mean is None
-    mom = 0.0 if bn.momentum is None else float(bn.momentum)
-    track = bn.training and bn.track_running_stats
-    if track:
-        bump_counter(bn)
-        if bn.momentum is None:
-            mom = 1.0 / float(bn.num_batches_tracked)
-    rm, rv = (bn.running_mean, bn.running_var) if (track or not use_batch) else (None, None)
-    return _BNActPool.apply(h, bn.weight, bn.bias, rm, rv, use_batch, mom, float(bn.eps), float(slope), num_clouds,
-                            n_per, with_mean)
+    use_batch, mom, rm, rv, eps = bn_mode(bn, h.shape[0])
+    return _BNActPool.apply(h, bn.weight, bn.bias, rm, rv, use_batch, mom, eps, float(slope), num_clouds, n_per, with_mean)

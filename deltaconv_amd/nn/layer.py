@@ -23,7 +23,7 @@ block but the last of a stream is [GEMM + statistics epilogue -> BatchNorm/activ
 the fusions above.  The edge MLP of a centralized first layer with depth > 1 (BatchNorm over the edges between two products) is
 computed in front of the node -- depth 2 x 64 channels on csrc/edge2.hip (chained fp32-MFMA products over the edges), other shapes
 through dc_edge_diff / dc_seg_reduce -- and enters it as ``x_max``; so does a depth-1 one under synchronised BatchNorm.
-Under synchronised BatchNorm (deltaconv_amd/dp.py) the node is unchanged: fused.linear_stats / bn_block_backward / _vn_backward
+Under synchronised BatchNorm (deltaconv_amd/dp.py) the node is unchanged: fused.linear_stats / bn_block_backward / vn_backward
 all-reduce the fp64 sums their kernels hand out between a product and its finaliser.
 
 Dense GEMMs: hand-written fp32-MFMA kernels (csrc/gemm.hip forward + input gradient, the forward ones with the
@@ -95,54 +95,6 @@ def _adopt(t, rows, cols, width):
     return None
 
 
-def _bn_mode(bn):
-    """-> (use_batch_stats, momentum, running_mean, running_var) and bumps num_batches_tracked."""
-    use_batch = bn.training or bn.running_mean is None
-    mom = 0.0 if bn.momentum is None else float(bn.momentum)
-    track = bn.training and bn.track_running_stats
-    if track:
-        fused.bump_counter(bn)
-        if bn.momentum is None:
-            mom = 1.0 / float(bn.num_batches_tracked)
-    rm, rv = (bn.running_mean, bn.running_var) if (track or not use_batch) else (None, None)
-    return use_batch, mom, rm, rv
-
-
-def _bn_backward(dy, lddy, h, coef, use, gamma, slope):
-    """-> (dh, dgamma, dbeta) of y = leaky(bn(h)) for the incoming dy (row stride lddy)."""
-    r, c = h.shape
-    dev = h.device
-    dh = torch.empty_like(h)
-    dg, db = torch.empty(c, dtype=_F32, device=dev), torch.empty(c, dtype=_F32, device=dev)
-    ws, nb = fused._ws(r, c, dev)
-    lib.call("dc_bn_act_backward", dy, lddy, h, c, r, c, coef[2], coef[3], coef[0], coef[1], gamma, slope, int(use),
-             dh, c, dg, db, ws, nb)
-    return dh, dg, db
-
-
-def _vn_backward(dout, lddo, h, combine, coef, use, gamma):
-    """-> (dh, dgamma, dbeta) of the vector non-linearity on h ([2n, co], or interleaved (P, Q) [2n, 2co])."""
-    ld = h.shape[1]
-    co = ld // 2 if combine else ld
-    n = h.shape[0] // 2
-    dev = h.device
-    dh = torch.empty_like(h)
-    dg, db = torch.empty(co, dtype=_F32, device=dev), torch.empty(co, dtype=_F32, device=dev)
-    ws, nb = fused._ws(n, co, dev)
-    group = fused.group_of(use)      # the group the FORWARD statistics were reduced over (fused.BatchStats)
-    if group is not None:        # synchronised statistics: this rank's sums -> all-reduce -> apply with the global means
-        stats, local = fused._sync_stats(("dc_vn_backward_sums", lambda out: (dout, lddo, h, ld, combine, n, co, coef[2], coef[3],
-                                                                              coef[0], coef[1], out, ws, nb)), co, n, dev, group)
-        m = torch.empty(2, co, dtype=_F32, device=dev)
-        lib.call("dc_sync_means", stats, co, m[0], m[1], dg, db)             # global means + this rank's dgamma / dbeta
-        lib.call("dc_vn_backward_apply", dout, lddo, h, ld, combine, n, co, coef[2], coef[3], coef[0], coef[1], gamma, 1,
-                 m[0], m[1], dh, ld)
-        return dh, dg, db
-    lib.call("dc_vn_backward", dout, lddo, h, ld, combine, n, co, coef[2], coef[3], coef[0], coef[1], gamma, int(use),
-             dh, ld, dg, db, ws, nb)
-    return dh, dg, db
-
-
 class DeltaConvLayerFn(torch.autograd.Function):
     """apply(x, v, x_max_or_None, cfg, *params); params = (W, gamma, beta) per block: the s_mlp_max blocks (none when
     x_max is given), the s_mlp blocks, the v_mlp blocks (none for a layer without vector stream)."""
@@ -154,7 +106,7 @@ class DeltaConvLayerFn(torch.autograd.Function):
         # of zeros per step (7 + 18 us at the bench shape)
         ctx.set_materialize_grads(False)
         g = cfg.graph
-        n, k = g.n, g.k
+        n = g.n
         (x, ldx), (v, ldv) = _rows(x), _rows(v)
         dev = x.device
         ci = x.shape[1]
@@ -213,16 +165,9 @@ class DeltaConvLayerFn(torch.autograd.Function):
                 bn_m, slope_m = cfg.bns_m[-1], cfg.slopes_m[-1]
                 if cfg.centralized:                      # depth 1 only (DeltaConv.forward routes depth > 1 outside)
                     y0 = fused.mm_nt(inp, Wm)
-                    stat = torch.empty(3, n, co, **f32)
-                    args = torch.empty(2, n, co, dtype=torch.uint8, device=dev)
-                    use_m, mom, rm, rv = _bn_mode(bn_m)
-                    coef_m = torch.empty(4, co, **f32)
-                    ws, nb = fused._ws(n, co, dev)
-                    if not use_m:
-                        coef_m = fused.eval_coeffs(gm, bm, rm, rv, float(bn_m.eps), co)
-                    call("dc_edge_gather_stats", y0, co, g.nbr, n, k, co, int(use_m), gm, bm, float(bn_m.eps), mom,
-                         rm if use_m else None, rv if use_m else None, stat[0], stat[1], args[0], args[1], stat[2],
-                         coef_m[0], coef_m[1], coef_m[2], coef_m[3], ws, nb)
+                    mode_m = fused.bn_mode(bn_m)         # (no row check: statistics over the edges)
+                    use_m = mode_m[0]
+                    stat, args, coef_m = fused.edge_gather_stats(y0, g, mode_m, gm, bm)
                     argsel = torch.empty(n, co, dtype=torch.uint8, device=dev)   # the selected slot: backward from the tile plan
                     # (applied below, behind the last s_mlp block, whose BatchNorm / activation / residual add it takes along)
                     pending_edge = (stat, args, coef_m, slope_m, argsel)
@@ -388,7 +333,8 @@ class DeltaConvLayerFn(torch.autograd.Function):
             for j in range(nv - 1, -1, -1):
                 inp, h, coef = svv[j]
                 W, gv, _ = pv[j]
-                dh, dg, db = _vn_backward(dcur, ldd, h, 2 if j == 0 else 0, coef, use_v[j], gv)
+                # (the group the FORWARD statistics were reduced over: fused.BatchStats)
+                dh, dg, db = fused.vn_backward(dcur, ldd, h, 2 if j == 0 else 0, coef, gv, use_v[j], fused.group_of(use_v[j]))
                 if j == 0:
                     Wst = W.view(2 * W.shape[0], K)
                     if need_v or need_x:
