@@ -123,3 +123,43 @@ def synthetic_batch(num_clouds, n, seed=0, normals=True, num_classes=40, per_poi
         cat = torch.zeros(len(sizes), categories)
         cat[torch.arange(len(sizes)), torch.randint(0, categories, (len(sizes),), generator=gen)] = 1
     return Batch(pos, torch.cat(bs), torch.cat(ns) if normals else None, None, y, cat, len(sizes))
+
+
+def synthetic_mesh(n_faces, seed=0, zero_area=0, shrink=None, labels=False):
+    """A seeded triangle mesh of ``n_faces`` triangles for tests and tools/bench_mesh_sample.py: a UV-grid torus (major radius
+    0.6, minor radius 0.3; closed when ``n_faces = 2 nu nv``, otherwise the first ``n_faces`` triangles of the smallest grid that
+    has them) whose vertices are moved along the surface by a seeded offset, so the face areas differ.
+    zero_area: that many zero-area faces ``(i, i, j)`` are appended (on top of ``n_faces``).
+    shrink = (count, factor): the first ``count`` faces get vertices of their own, pulled towards the face's corner 0 by
+    ``factor`` (their area shrinks by ``factor ** 2``).
+    -> ``(pos float32 [V,3], face int64 [3,F])`` as the mesh readers give them, and with ``labels`` an int64 [V] label per vertex."""
+    n_faces = int(n_faces)
+    if n_faces < 1:
+        raise ValueError("synthetic_mesh: n_faces >= 1")
+    gen = torch.Generator().manual_seed(int(seed))
+    quads = -(-n_faces // 2)
+    nv = max(3, int(quads ** 0.5))
+    nu = max(3, -(-quads // nv))
+    u = (torch.arange(nu, dtype=torch.float64)[:, None] + 0.6 * (torch.rand(nu, nv, generator=gen, dtype=torch.float64) - 0.5)) * (2 * torch.pi / nu)
+    v = (torch.arange(nv, dtype=torch.float64)[None, :] + 0.6 * (torch.rand(nu, nv, generator=gen, dtype=torch.float64) - 0.5)) * (2 * torch.pi / nv)
+    ring = 0.6 + 0.3 * torch.cos(v)
+    pos = torch.stack([ring * torch.cos(u), ring * torch.sin(u), 0.3 * torch.sin(v)], dim=-1).reshape(-1, 3)
+    i, j = torch.meshgrid(torch.arange(nu), torch.arange(nv), indexing="ij")
+    a, b, c, d = i * nv + j, ((i + 1) % nu) * nv + j, ((i + 1) % nu) * nv + (j + 1) % nv, i * nv + (j + 1) % nv
+    face = torch.stack([torch.stack([a, b, c], -1), torch.stack([a, c, d], -1)], dim=2).reshape(-1, 3)[:n_faces]
+    if shrink is not None:
+        count, factor = int(shrink[0]), float(shrink[1])
+        if not 0 <= count <= n_faces:
+            raise ValueError("synthetic_mesh: shrink = (count <= n_faces, factor)")
+        tri = pos[face[:count]]                                        # [count, 3 corners, 3]
+        own = tri[:, :1] + factor * (tri - tri[:, :1])
+        face = face.clone()
+        face[:count] = pos.shape[0] + torch.arange(3 * count).reshape(count, 3)
+        pos = torch.cat([pos, own.reshape(-1, 3)])
+    if zero_area:
+        k = torch.arange(int(zero_area)) % pos.shape[0]
+        face = torch.cat([face, torch.stack([k, k, (k + 1) % pos.shape[0]], -1)])
+    out = (pos.float(), face.t().contiguous().long())
+    if labels:
+        out = out + (torch.randint(0, 8, (pos.shape[0],), generator=gen),)
+    return out

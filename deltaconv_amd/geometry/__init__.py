@@ -3,3 +3,4 @@ from .grad_div_mls import *       # noqa: F401,F403
 from .graph import Graph, knn_graph, as_graph  # noqa: F401
 from .utils import batch_dot      # noqa: F401
 from .fps import geodesic_fps, geodesic_fps_batch    # noqa: F401
+from .mesh_sample import sample_points_batch         # noqa: F401

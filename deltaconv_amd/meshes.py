@@ -1,0 +1,130 @@
+"""Device-resident triangle meshes and their surface sampling: all meshes of a dataset concatenated in HBM, ``num`` points
+drawn on every one of them in two launches per group of meshes (csrc/mesh.hip: ``dc_mesh_sample``).
+
+What it replaces: the ``SamplePoints`` step of the reference's data preparation (deltaconv/transforms/sample_points.py:22-59,
+called per shape from the ``pre_transform`` of experiments/train_modelnet.py:30-34, train_shrec.py:30-34 and
+train_shapeseg.py:28-34) -- a ``torch.multinomial`` over the faces and a handful of small ATen calls per shape.
+
+    meshes = DeviceMeshDataset.from_dataset(ModelNet(root, None, "40", True, pre_transform=T.NormalizeScale()), device)
+    store = meshes.sample_points(num_points * sampling_margin, seed=1).geodesic_subsample(num_points, seed=1)
+    loader = DeviceLoader(store, 32, shuffle=True, drop_last=True, transform=aug, seed=1)
+
+A mesh's sample is a function of ``(mesh, seed, round, dataset index)`` only (csrc/mesh_math.h): it does not depend on how
+meshes are grouped into launches, and another ``round`` gives a fresh sample of the same store.  There is no CPU path.
+"""
+import numpy as np
+import torch
+
+from .geometry.mesh_sample import sample_points_batch
+from .loader import DeviceDataset
+
+__all__ = ["DeviceMeshDataset", "sample_points_batch", "MESH_MAX_FACES"]
+
+MESH_MAX_FACES = 1 << 24          # faces per mesh (csrc/mesh_math.h: the sum of the integer face weights stays below 2^57)
+
+
+def _offsets(counts):
+    ptr = np.zeros(len(counts) + 1, dtype=np.int64)
+    ptr[1:] = np.cumsum(np.asarray(counts, dtype=np.int64))
+    return ptr
+
+
+class DeviceMeshDataset:
+    """All meshes of a dataset concatenated on the device + their vertex and face counts on the host."""
+
+    def __init__(self, vert, face, vptr, fptr, n_verts, n_faces, y_vert=None, y_cloud=None, category=None):
+        self.vert, self.face, self.vptr, self.fptr = vert, face, vptr, fptr      # [Vs,3] f32, [Fs,3] i32 (local ids), [S+1] i64 x 2
+        self.n_verts = np.asarray(n_verts, dtype=np.int64)                        # host
+        self.n_faces = np.asarray(n_faces, dtype=np.int64)                        # host
+        self.y_vert, self.y_cloud, self.category = y_vert, y_cloud, category
+        self.device = vert.device
+        self.total = self.degenerate = None                                       # of the last sample_points pass
+
+    def __len__(self):
+        return int(self.n_faces.shape[0])
+
+    @classmethod
+    def from_dataset(cls, ds, device):
+        """ds: a dataset with ``.items`` (ModelNet / ShapeSeg read with a ``pre_transform`` that keeps the faces; its
+        ``transform`` is not run) or any sequence of items with ``pos [V,3]`` and ``face [3,F]`` as the OFF / PLY / OBJ readers
+        give them.  Optional ``y`` (one per vertex or one per cloud) and ``category``, each on every item or on none.  Raises
+        ``ValueError`` unless every mesh has ``V >= 1``, ``1 <= F <= 2^24`` and every face id in ``[0, V)``."""
+        items = list(ds.items if hasattr(ds, "items") and not callable(ds.items) else ds)
+        if not items:
+            raise ValueError("DeviceMeshDataset: empty dataset")
+        verts, faces = [], []
+        for i, d in enumerate(items):
+            p, f = getattr(d, "pos", None), getattr(d, "face", None)
+            if p is None or f is None:
+                raise ValueError(f"DeviceMeshDataset: item {i} has no pos / face (was SamplePoints already run in pre_transform?)")
+            if p.dim() != 2 or p.shape[1] != 3 or p.shape[0] < 1:
+                raise ValueError(f"DeviceMeshDataset: item {i}: pos must be [V,3] with V >= 1, got {tuple(p.shape)}")
+            if f.dim() != 2 or f.shape[0] != 3 or f.is_floating_point():
+                raise ValueError(f"DeviceMeshDataset: item {i}: face must be integer [3,F], got {f.dtype} {tuple(f.shape)}")
+            if not 1 <= f.shape[1] <= MESH_MAX_FACES:
+                raise ValueError(f"DeviceMeshDataset: item {i} has {f.shape[1]} faces, supported: 1 .. 2^24")
+            if int(f.min()) < 0 or int(f.max()) >= p.shape[0]:
+                raise ValueError(f"DeviceMeshDataset: item {i}: face ids {int(f.min())} .. {int(f.max())} outside its "
+                                 f"{p.shape[0]} vertices")
+            verts.append(p.float())
+            faces.append(f.t().to(torch.int32))
+        n_verts, n_faces = [int(p.shape[0]) for p in verts], [int(f.shape[0]) for f in faces]
+
+        def column(name):
+            vals = [getattr(d, name, None) for d in items]
+            return vals if all(v is not None for v in vals) else None
+
+        ys, y_vert, y_cloud = column("y"), None, None
+        if ys is not None:
+            ys = [(v if torch.is_tensor(v) else torch.tensor([v])).reshape(-1) for v in ys]
+            if any(v.is_floating_point() for v in ys):
+                raise ValueError("DeviceMeshDataset: labels must be integers")
+            if all(v.numel() == 1 for v in ys):
+                y_cloud = torch.cat(ys).long()
+            elif all(v.numel() == n for v, n in zip(ys, n_verts)):
+                y_vert = torch.cat(ys).long()
+            else:
+                raise ValueError("DeviceMeshDataset: y must hold one label per cloud or one per vertex")
+        cats = column("category")
+        category = torch.stack([c.reshape(-1) for c in cats]).float() if cats is not None else None
+        up = lambda t: None if t is None else t.contiguous().to(device)
+        return cls(up(torch.cat(verts)), up(torch.cat(faces)), up(torch.from_numpy(_offsets(n_verts))),
+                   up(torch.from_numpy(_offsets(n_faces))), n_verts, n_faces, up(y_vert), up(y_cloud), up(category))
+
+    def sample_points(self, num, include_normals=True, include_labels=False, seed=0, round=0, meshes_per_launch=4096):
+        """``T.SamplePoints(num, include_normals=, include_labels=)`` for the whole store on the device -> a ``DeviceDataset`` whose
+        clouds each hold ``num`` points (``geodesic_subsample`` takes it from there).  ``norm`` is set with ``include_normals``;
+        ``y_point`` from the per-vertex labels (corner 0 of the picked face) with ``include_labels``, otherwise ``y_cloud`` and
+        ``category`` pass through.  Draws are a function of ``(seed, round, dataset index, sample index)``, whatever
+        ``meshes_per_launch`` is (the workspace holds 8 bytes per face of a group).  The per-mesh sums of the face weights are
+        kept as ``total`` (device) and ``degenerate`` (host bool array, ``total == 0``: every face of that mesh has zero area
+        and it was sampled uniformly by face index) on this store and on the result -- one synchronise at the end of the pass."""
+        num, s, dev, per = int(num), len(self), self.device, int(meshes_per_launch)
+        if num < 1 or not 1 <= per <= 65535:
+            raise ValueError("sample_points: num >= 1 and 1 <= meshes_per_launch <= 65535")
+        if not 0 <= int(seed) < 2 ** 32 or int(round) < 0:
+            raise ValueError("sample_points: seed in [0, 2^32) and round >= 0")
+        if include_labels and self.y_vert is None:
+            raise ValueError("sample_points: include_labels needs one label per vertex on every mesh")
+        pos = torch.empty((s * num, 3), dtype=torch.float32, device=dev)
+        norm = torch.empty((s * num, 3), dtype=torch.float32, device=dev) if include_normals else None
+        y = torch.empty(s * num, dtype=torch.int64, device=dev) if include_labels else None
+        total = torch.empty(s, dtype=torch.int64, device=dev)
+        fhost = _offsets(self.n_faces)
+        for lo in range(0, s, per):
+            hi = min(s, lo + per)
+            cut = lambda t: None if t is None else t[lo * num:hi * num]
+            out = {"pos": cut(pos), "total": total[lo:hi]}
+            if include_normals:
+                out["norm"] = cut(norm)
+            if include_labels:
+                out["y"] = cut(y)
+            sample_points_batch(self.vert, self.face, self.vptr[lo:hi + 1], self.fptr[lo:hi + 1], num, first_mesh_index=lo,
+                                seed=seed, round=round, y_vert=self.y_vert if include_labels else None, normals=include_normals,
+                                labels=include_labels, n_faces=int(fhost[hi] - fhost[lo]), out=out)
+        ptr = torch.arange(s + 1, dtype=torch.int64, device=dev) * num
+        store = DeviceDataset(pos, ptr, np.full(s, num, dtype=np.int64), norm, None, y,
+                              None if include_labels else self.y_cloud, self.category)
+        self.total = store.total = total
+        self.degenerate = store.degenerate = total.cpu().numpy() == 0             # the one synchronise of the pass
+        return store

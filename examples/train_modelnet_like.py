@@ -4,7 +4,8 @@ epoch, state_dict checkpoints with the reference's key names -- on the MI355X pa
 the GPUs of one node.  No dataset ships with this repo (the reference downloads ModelNet40), so by default
 the clouds are synthetic; with `--data <ModelNet40 root>` (raw/<category>/<train|test>/*.off) the reference's
 pipeline runs instead: NormalizeScale -> SamplePoints -> GeodesicFPS once, RandomScale + RandomTranslateGlobal
-per access (train_modelnet.py:29-49), through `deltaconv_amd.datasets`.
+per access (train_modelnet.py:29-49), through `deltaconv_amd.datasets`.  `--device-loader` keeps the prepared clouds on
+the GPU; `--device-fps` and `--device-sample` move GeodesicFPS, and SamplePoints with it, there as well.
 
     python examples/train_modelnet_like.py --epochs 3
     python examples/train_modelnet_like.py --data /data/ModelNet40 --epochs 50
@@ -86,7 +87,13 @@ def main():
     ap.add_argument("--device-fps", action="store_true",
                     help="with --device-loader: GeodesicFPS leaves pre_transform; the oversampled clouds are reduced to num_points on "
                          "the device, all shapes in a few launches (DeviceDataset.geodesic_subsample) instead of one host call per shape")
+    ap.add_argument("--device-sample", action="store_true",
+                    help="with --device-loader: SamplePoints and GeodesicFPS leave pre_transform (NormalizeScale alone stays); the "
+                         "meshes go to the GPU and are sampled and reduced there, all shapes in a few launches "
+                         "(DeviceMeshDataset.sample_points, then DeviceDataset.geodesic_subsample)")
     args = ap.parse_args()
+    if args.device_sample and not (args.data is not None and args.device_loader):
+        raise SystemExit("--device-sample samples device-resident meshes: it needs --data and --device-loader")
     if args.device_fps and not (args.data is not None and args.device_loader):
         raise SystemExit("--device-fps samples a device-resident dataset: it needs --data and --device-loader")
     if args.device_eval and not (args.data is not None and args.device_loader):
@@ -110,15 +117,22 @@ def main():
         from deltaconv_amd.datasets import Compose, DataLoader, ModelNet
         pre = (T.NormalizeScale(), T.SamplePoints(args.num_points * args.sampling_margin, include_normals=True))
         pre = Compose(pre if args.device_fps else pre + (T.GeodesicFPS(args.num_points),))
+        if args.device_sample:                                   # the meshes themselves are stored: faces stay
+            pre = T.NormalizeScale()
         aug = Compose((T.RandomScale((4 / 5, 5 / 4)), T.RandomTranslateGlobal(0.1)))
         tr = ModelNet(args.data, None, "40", True, transform=aug, pre_transform=pre)
         te = ModelNet(args.data, None, "40", False, pre_transform=pre)
     if args.data is not None and args.device_loader:
         # the same recipe, drawn and applied on the device; every rank takes its share of one permutation per epoch
         fps = args.num_points if args.device_fps else None      # same start points on every rank: one dataset, many shares
-        train = deltaconv.DeviceLoader(deltaconv.DeviceDataset.from_dataset(tr, dev, fps=fps, fps_seed=1), args.batch_size,
-                                       shuffle=True, drop_last=True, transform=aug, seed=1, rank=rank, world=world)
-        test = deltaconv.DeviceLoader(deltaconv.DeviceDataset.from_dataset(te, dev, fps=fps, fps_seed=1), args.batch_size)
+        if args.device_sample:                                  # same draws on every rank: seeds, not the global generator
+            store = lambda ds: deltaconv.DeviceMeshDataset.from_dataset(ds, dev).sample_points(
+                args.num_points * args.sampling_margin, seed=1).geodesic_subsample(args.num_points, seed=1)
+        else:
+            store = lambda ds: deltaconv.DeviceDataset.from_dataset(ds, dev, fps=fps, fps_seed=1)
+        train = deltaconv.DeviceLoader(store(tr), args.batch_size, shuffle=True, drop_last=True, transform=aug, seed=1, rank=rank,
+                                       world=world)
+        test = deltaconv.DeviceLoader(store(te), args.batch_size)
         args.train_batches = len(train)
         if args.device_eval:                 # equal-size clouds (GeodesicFPS to num_points): the full batches replay one graph
             evaluator = deltaconv.DeviceEvaluator(model, test, task="classification")

@@ -725,6 +725,41 @@ int dc_geodesic_fps_batch(const void* pos, int32_t pos_is_f64, const int64_t* pt
                           int32_t n_samples, const int32_t* start, int32_t* out, void* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* ---- surface sampling of a batch of triangle meshes (csrc/mesh.hip, csrc/mesh_math.h) ------------------------------------------ */
+/* Bytes of workspace dc_mesh_sample needs for meshes of F_total faces in all: the cdf, 8 bytes per face.  Reference:
+ * deltaconv/transforms/sample_points.py:22-59 (the area vector of :29-32 is the only state between its stages). */
+size_t dc_mesh_sample_workspace_bytes(int64_t F_total);
+/* Faces one iteration of the cdf kernel's workgroup scan covers: the sizes around which its tests are placed. */
+int32_t dc_mesh_scan_faces(void);
+/* Replaces the per-shape host call in front of GeodesicFPS in the reference's data preparation -- deltaconv/transforms/
+ * sample_points.py:22-59 as called by experiments/train_modelnet.py:30-34, train_shrec.py:30-34 and train_shapeseg.py:28-34:
+ * `num` points on the surface of each of B meshes, faces drawn with a probability proportional to their area, uniform barycentric
+ * coordinates with the fold of :36-38, the point as (p0 + f1 e1) + f2 e2 (:46-48), the normal by F.normalize of e1 x e2 (:41-44),
+ * the label of corner 0 (:53-54).  Areas are fp64 and cut to integer weights in [0, 2^32] relative to the mesh's largest face;
+ * the cdf is their uint64 running sum and a draw picks the first face whose cdf exceeds (u * total) >> 64 -- integer and
+ * order-free, so the picks are a function of (mesh, seed, round, dataset index, sample index) only (csrc/mesh_math.h); the
+ * division by pos.max() of :26-27 is not restated.  Draws: Philox-4x32-10, key (seed, 0x6D657368), counter (sample index,
+ * first_mesh_index + b, round lo, round hi): a mesh's sample does not depend on how meshes are grouped into calls.
+ *   vert       DEVICE [Vs,3] fp32 vertex rows of the store
+ *   face       DEVICE [Fs,3] vertex ids LOCAL to the mesh, one row per triangle; a row with an id outside [0, V) has weight 0 and
+ *              is never indexed
+ *   vptr, fptr DEVICE [B+1] ABSOLUTE row offsets of the B meshes of this call into vert / face (a slice of the store's offsets)
+ *   y_vert     DEVICE [Vs] per-vertex labels, or NULL (required for y)
+ *   pos        DEVICE [B*num,3]; norm [B*num,3], y [B*num], face_id [B*num] (local to the mesh) or NULL
+ *   total      DEVICE [B] or NULL: the sum of a mesh's weights; 0 = every face degenerate (such a mesh is sampled uniformly
+ *              by face index), -1 = the mesh's cdf did not fit the workspace (the mesh is skipped: zero rows, face_id -1)
+ *   workspace  DEVICE, 8-byte aligned, dc_mesh_sample_workspace_bytes(fptr[B] - fptr[0]) bytes; it holds the cdf on return,
+ *              mesh b at element fptr[b] - fptr[0]
+ * num < 1, B above 65 535, seed outside [0, 2^32), a negative round, dataset indices past 2^32 or y without y_vert: DC_ERR_ARG; a
+ * workspace below 8 bytes per mesh: DC_ERR_WORKSPACE; both with a message, checked before anything touches the device.  The
+ * offsets are device arrays, so the face count itself is held to the workspace by the kernels (total = -1 above).  B = 0
+ * returns DC_OK.  A mesh has at most 2^24 faces (the caller's to check: total < 2^57).  Two launches, stream-ordered, no
+ * allocation, no synchronisation, no atomics: the outputs are a function of the inputs only. */
+int dc_mesh_sample(const float* vert, const int32_t* face, const int64_t* vptr, const int64_t* fptr, int32_t B,
+                   int64_t first_mesh_index, int32_t num, int64_t seed, int64_t round, const int64_t* y_vert,
+                   float* pos, float* norm, int64_t* y, int32_t* face_id, int64_t* total,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
