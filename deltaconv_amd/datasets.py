@@ -243,7 +243,10 @@ class ShapeNet(torch.utils.data.Dataset):
     ``root/raw/train_test_split/shuffled_{train,val,test}_file_list.json``.  Items carry ``pos``, ``norm``,
     per-point ``y`` (0..49) and the one-hot ``category`` [1,16] indexed within the SELECTED categories, as the
     reference builds it; ``y_mask[c]`` marks the part labels of category c.  Processed splits are cached as
-    ``root/processed/<cats>_{train,val,test,trainval}.pt``."""
+    ``root/processed/<cats>_{train,val,test,trainval}.pt``.  The cache is keyed by the categories alone: it holds what the
+    ``pre_transform`` of the constructor that WROTE it made, and a later constructor with another ``pre_transform`` reads that.
+    Two differently prepared copies of one root (subsampled for training, every point for full-resolution evaluation) therefore
+    need two caches: ``processed_dir`` (default ``root/processed``) names the one to read or write."""
 
     _names = ['Airplane', 'Bag', 'Cap', 'Car', 'Chair', 'Earphone', 'Guitar', 'Knife', 'Lamp', 'Laptop', 'Motorbike',
               'Mug', 'Pistol', 'Rocket', 'Skateboard', 'Table']
@@ -255,7 +258,7 @@ class ShapeNet(torch.utils.data.Dataset):
     splits = ['train', 'val', 'test', 'trainval']
 
     def __init__(self, root, categories=None, n_per_class=None, include_normals=True, split='trainval', transform=None,
-                 pre_transform=None, pre_filter=None):
+                 pre_transform=None, pre_filter=None, processed_dir=None):
         if categories is None:
             categories = list(self.category_ids.keys())
         if isinstance(categories, str):
@@ -266,7 +269,8 @@ class ShapeNet(torch.utils.data.Dataset):
         self.root, self.categories, self.n_per_class = root, categories, n_per_class
         self.transform, self.pre_transform, self.pre_filter = transform, pre_transform, pre_filter
         self.include_normals = include_normals
-        self.raw_dir, self.processed_dir = osp.join(root, "raw"), osp.join(root, "processed")
+        self.raw_dir = osp.join(root, "raw")
+        self.processed_dir = osp.join(root, "processed") if processed_dir is None else processed_dir
         tag = '_'.join(c[:3].lower() for c in categories)
         paths = {s: osp.join(self.processed_dir, f"{tag}_{s}.pt") for s in self.splits}
         if not all(osp.exists(p) for p in paths.values()):

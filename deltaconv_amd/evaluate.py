@@ -145,9 +145,20 @@ class DeviceEvaluator:
     Returns the keys of ``utils.evaluate_votes``: ``accuracy``, ``balanced_accuracy`` (the mean over the classes with
     cnt > 0 of hit / cnt), ``ignored`` (rows whose label lies outside the classes), with categories ``mean_iou``, ``ious``
     and ``label``, with `keep_pred` ``pred`` and ``true`` ([clouds, points] for equal-size clouds, flat otherwise).
-    `class_choice` picks the parts as ``calc_shape_IoU`` does (``part_tables``)."""
+    `class_choice` picks the parts as ``calc_shape_IoU`` does (``part_tables``).
 
-    def __init__(self, model, loader, task="segmentation", num_votes=1, class_choice=None, graphed=True, keep_pred=False):
+    ``propagate_to`` (segmentation only): the store the loader's clouds were sampled from -- a ``DeviceDataset`` with ``y_point``
+    or a ``DeviceMeshDataset`` with ``y_vert``, the same clouds in the same order.  The k = ``propagate_k`` nearest sampled points
+    of every target row are found once, here (``Propagator``: csrc/interp.hip).  On the LAST vote, after a batch's metric launch,
+    the batch's vote sums (one vote: its logits) are interpolated to the target rows of its clouds and scored against the
+    target's labels by a second ``dc_eval_metrics`` launch.  ``run()`` then returns the keys above at TARGET resolution plus
+    ``"sampled"``: the same keys at the sampled points, exactly what it returns without ``propagate_to`` (with `keep_pred` the
+    target-resolution ``pred`` and ``true`` are flat, one entry per target row in store order).  Still one synchronise
+    per pass; inference only (no autograd through the interpolation).  ``propagate_to=None``: nothing changes, down to the
+    launch list."""
+
+    def __init__(self, model, loader, task="segmentation", num_votes=1, class_choice=None, graphed=True, keep_pred=False,
+                 propagate_to=None, propagate_k=3):
         if task not in ("segmentation", "classification"):
             raise ValueError(f"DeviceEvaluator: task must be 'segmentation' or 'classification', got {task!r}")
         if loader.shuffle:
@@ -190,6 +201,18 @@ class DeviceEvaluator:
             self.step = GraphedEvalStep(model, loader.static_batch())
         self._cls_ptr = {}
         self.hit = self.cnt = self.ignored = self.iou = self.pred = self.votes = None
+        self.prop = self.full = None
+        if propagate_to is not None:
+            from .propagate import Propagator, target_view
+            if not self.seg:
+                raise ValueError("DeviceEvaluator: propagate_to is for segmentation (labels per point)")
+            if loader.world != 1:
+                raise ValueError("DeviceEvaluator: propagate_to needs the whole set on one rank (a batch is a contiguous range of "
+                                 "the store's clouds)")
+            self.full_y = target_view(propagate_to)[3]
+            if self.full_y is None:
+                raise ValueError("DeviceEvaluator: propagate_to must carry one label per point (y_point) or per vertex (y_vert)")
+            self.prop = Propagator(store, propagate_to, k=propagate_k)
 
     # ---- buffers, made at the first batch (the class count is the width of the logits) ------------------------------------
     def _alloc(self, P):
@@ -203,9 +226,15 @@ class DeviceEvaluator:
         self.iou = torch.zeros(self.groups, dtype=torch.float64, device=dev) if self.has_parts else None
         self.pred = torch.zeros(rows, dtype=torch.int64, device=dev) if self.keep_pred else None
         self.votes = torch.zeros(rows, P, dtype=torch.float32, device=dev) if self.num_votes > 1 else None
+        if self.prop is not None:                               # the same result rows at target resolution
+            trows = int(self.prop.toff[-1])
+            self.full = dict(hit=torch.zeros_like(self.hit), cnt=torch.zeros_like(self.cnt), ignored=torch.zeros_like(self.ignored),
+                             iou=None if self.iou is None else torch.zeros_like(self.iou),
+                             pred=torch.zeros(trows, dtype=torch.int64, device=dev) if self.keep_pred else None)
 
-    def _metrics(self, i, batch, logits):
-        """One launch: batch i of the pass (its clouds start at cloud i * batch_size of the share)."""
+    def _metrics(self, i, batch, logits, last=False):
+        """One launch: batch i of the pass (its clouds start at cloud i * batch_size of the share).  With ``propagate_to``, on the
+        last vote, two more: the interpolation to the target rows of the batch's clouds and their metrics."""
         if logits.dim() != 2 or logits.dtype != torch.float32:
             raise TypeError("DeviceEvaluator: the model must return fp32 logits [rows, classes]")
         if self.hit is None:
@@ -225,6 +254,16 @@ class DeviceEvaluator:
                      0 if cat is None else cat.shape[1], self.part_start if self.has_parts else None,
                      self.part_count if self.has_parts else None, pred, None if self.iou is None else self.iou[c0:c0 + B],
                      self.hit[c0:c0 + B], self.cnt[c0:c0 + B], self.ignored[c0:c0 + B])
+            if self.prop is not None and last:
+                _, _, tptr32, (t0, t1), _ = self.prop.cloud_range((c0, c0 + B))
+                if t1 > t0:
+                    up = self.prop.apply(logits if votes is None else votes, (c0, c0 + B))
+                    f = self.full
+                    lib.call("dc_eval_metrics", up, up.stride(0), None, self.full_y[t0:t1], tptr32, B, t1 - t0, P, cat,
+                             0 if cat is None else cat.shape[1], self.part_start if self.has_parts else None,
+                             self.part_count if self.has_parts else None, None if f["pred"] is None else f["pred"][t0:t1],
+                             None if f["iou"] is None else f["iou"][c0:c0 + B], f["hit"][c0:c0 + B], f["cnt"][c0:c0 + B],
+                             f["ignored"][c0:c0 + B])
         else:
             ptr = self._cls_ptr.get(B)
             if ptr is None:
@@ -240,11 +279,11 @@ class DeviceEvaluator:
         try:
             if self.votes is not None:
                 self.votes.zero_()
-            for _ in range(self.num_votes):
+            for vote in range(self.num_votes):
                 it = self.loader.into(self.step.static, fresh_tail=True) if self.step is not None else iter(self.loader)
                 for i, batch in enumerate(it):
                     graphed = self.step is not None and batch is self.step.static
-                    self._metrics(i, batch, self.step.step() if graphed else model(batch))
+                    self._metrics(i, batch, self.step.step() if graphed else model(batch), last=vote == self.num_votes - 1)
         finally:
             model.train(was_training)
         return self._results()
@@ -260,6 +299,11 @@ class DeviceEvaluator:
         pull = lambda t: None if t is None else t.cpu().numpy()
         hit, cnt, ign, iou, label = pull(self.hit), pull(self.cnt), pull(self.ignored), pull(self.iou), pull(label)
         out = reduce_metrics(hit, cnt, ign, iou, label)
+        if self.full is not None:
+            f = self.full
+            top = reduce_metrics(pull(f["hit"]), pull(f["cnt"]), pull(f["ignored"]), pull(f["iou"]), label)
+            if self.keep_pred:
+                top.update(pred=pull(f["pred"]), true=pull(self.full_y))
         if self.keep_pred:
             pred = pull(self.pred)
             if self.seg:
@@ -271,4 +315,7 @@ class DeviceEvaluator:
             else:
                 true = pull(store.y_cloud[share_dev])
             out.update(pred=pred, true=true)
+        if self.full is not None:
+            top["sampled"] = out
+            return top
         return out

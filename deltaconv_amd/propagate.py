@@ -1,0 +1,132 @@
+"""Propagation of per-point values from a sampled, device-resident dataset back to the points or vertices it was sampled from
+(csrc/interp.hip: ``dc_knn_cross`` once per dataset, ``dc_knn_interpolate`` per use) -- PointNet++-style feature propagation,
+``torch_geometric.nn.knn_interpolate`` for a whole store.
+
+What it closes: every stage of the device pipeline (``DeviceMeshDataset.sample_points``, ``DeviceDataset.geodesic_subsample``)
+reduces resolution, and ``DeviceEvaluator`` scored the sampled points only; the part-segmentation benchmarks are defined on all
+points of a shape, or on a mesh's vertices.
+
+    full = DeviceDataset.from_dataset(test_set, device)                 # every point of every shape, with its labels
+    test = full.geodesic_subsample(2048, seed=1)                         # what the network sees
+    result = DeviceEvaluator(model, DeviceLoader(test, 16), num_votes=10, propagate_to=full).run()
+    result["mean_iou"], result["sampled"]["mean_iou"]                   # at full resolution / at the sampled points
+
+    prop = Propagator(test, meshes, k=3)                                 # target: a DeviceMeshDataset (its vertices)
+    vertex_logits = prop.apply(logits, (0, len(test)))
+
+Inference only: no autograd, no backward kernel.  There is no CPU path.
+"""
+import numpy as np
+import torch
+
+from .geometry.interpolate import MAX_K, interpolate_rows, knn_cross
+
+__all__ = ["Propagator", "target_view"]
+
+
+def target_view(target):
+    """-> (pos [rows,3], ptr int64 [S+1] on the device, sizes on the host, per-row labels or None) of a ``DeviceDataset`` (its
+    points) or a ``DeviceMeshDataset`` (its vertices)."""
+    if hasattr(target, "vert") and hasattr(target, "vptr"):
+        return target.vert, target.vptr, np.asarray(target.n_verts, dtype=np.int64), target.y_vert
+    if hasattr(target, "pos") and hasattr(target, "ptr") and hasattr(target, "sizes"):
+        return target.pos, target.ptr, np.asarray(target.sizes, dtype=np.int64), target.y_point
+    raise TypeError(f"Propagator: the target must be a DeviceDataset or a DeviceMeshDataset, got {type(target).__name__}")
+
+
+def _host_offsets(sizes):
+    off = np.zeros(len(sizes) + 1, dtype=np.int64)
+    off[1:] = np.cumsum(sizes)
+    return off
+
+
+class Propagator:
+    """The k nearest SOURCE points of every TARGET row, found once for the whole set, and the interpolation from them.
+
+    `source`: a ``DeviceDataset`` (the sampled clouds the network runs on).  `target`: a ``DeviceDataset`` (its ``pos``) or a
+    ``DeviceMeshDataset`` (its ``vert``) with the same number of clouds in the same order.  The constructor runs
+    ``dc_knn_cross`` over the set in groups of ``clouds_per_launch`` clouds, in STORE coordinates -- the loader's per-cloud
+    augmentations do not enter -- and keeps ``idx`` (int32, local to the source cloud, -1 = no such neighbour) and ``d2`` (fp32):
+    8 k bytes per target row.  No synchronise: the sizes are the stores' host arrays.
+
+    ``apply(values, clouds)`` interpolates source-resolution rows to target rows (``w = 1 / max(d^2, 1e-16)``, PyG's
+    ``knn_interpolate``); ``labels(pred)`` is the k = 1 label transfer, a gather.  Inference only: no autograd, no backward."""
+
+    def __init__(self, source, target, k=3, clouds_per_launch=4096):
+        k, per = int(k), int(clouds_per_launch)
+        if not 1 <= k <= MAX_K:
+            raise ValueError(f"Propagator: k = {k} outside [1, {MAX_K}]")
+        if not 1 <= per <= 65535:
+            raise ValueError("Propagator: 1 <= clouds_per_launch <= 65535")
+        if not (hasattr(source, "pos") and hasattr(source, "ptr") and hasattr(source, "sizes")):
+            raise TypeError(f"Propagator: the source must be a DeviceDataset, got {type(source).__name__}")
+        tpos, tptr, tsizes, _ = target_view(target)
+        if len(tsizes) != len(source):
+            raise ValueError(f"Propagator: {len(source)} source clouds but {len(tsizes)} target clouds (same clouds, same order)")
+        if tpos.device != source.pos.device:
+            raise ValueError("Propagator: source and target live on different devices")
+        self.source, self.target, self.k = source, target, k
+        self.device = tpos.device
+        self.tptr, self.sptr = tptr, source.ptr
+        self.tsizes, self.ssizes = tsizes, np.asarray(source.sizes, dtype=np.int64)
+        self.toff, self.soff = _host_offsets(self.tsizes), _host_offsets(self.ssizes)     # host copies of the offsets
+        rows, s = int(self.toff[-1]), len(source)
+        # every target row lies in exactly one cloud of the store, so the search writes every entry: no fill pass
+        self.idx = torch.empty((rows, k), dtype=torch.int32, device=self.device)
+        self.d2 = torch.empty((rows, k), dtype=torch.float32, device=self.device)
+        with torch.no_grad():
+            for lo in range(0, s, per):
+                hi = min(s, lo + per)
+                mq = int(self.tsizes[lo:hi].max())
+                if mq:
+                    knn_cross(tpos, source.pos, k, ptr_query=tptr[lo:hi + 1], ptr_ref=self.sptr[lo:hi + 1], max_query_cloud=mq,
+                              out=(self.idx, self.d2))
+        self._ranges = {}
+
+    def __len__(self):
+        return len(self.tsizes)
+
+    def cloud_range(self, clouds):
+        """The offsets of the contiguous cloud range ``(c0, c1)`` RELATIVE to its first row, built on the device from the stores'
+        offsets and kept: ``(target ptr int64, source ptr int64, target ptr int32, target rows (t0, t1), source rows (s0, s1))``."""
+        c0, c1 = int(clouds[0]), int(clouds[1])
+        if not 0 <= c0 <= c1 <= len(self):
+            raise ValueError(f"Propagator: clouds ({c0}, {c1}) outside [0, {len(self)}]")
+        r = self._ranges.get((c0, c1))
+        if r is None:
+            q = (self.tptr[c0:c1 + 1] - self.tptr[c0:c0 + 1]).contiguous()
+            s = (self.sptr[c0:c1 + 1] - self.sptr[c0:c0 + 1]).contiguous()
+            r = self._ranges[(c0, c1)] = (q, s, q.to(torch.int32), (int(self.toff[c0]), int(self.toff[c1])),
+                                          (int(self.soff[c0]), int(self.soff[c1])))
+        return r
+
+    @torch.no_grad()
+    def apply(self, values, clouds=None, out=None):
+        """values: DEVICE fp32 ``[source rows of the clouds, C]`` (rows may be strided), the clouds ``(c0, c1)`` a contiguous range
+        of the set (default: all) -> fp32 ``[target rows of those clouds, C]``.  One launch; no synchronise."""
+        clouds = (0, len(self)) if clouds is None else clouds
+        c0, c1 = int(clouds[0]), int(clouds[1])
+        q, s, _, (t0, t1), (s0, s1) = self.cloud_range((c0, c1))
+        if values.dim() != 2 or values.shape[0] != s1 - s0:
+            raise ValueError(f"Propagator.apply: values must hold the {s1 - s0} source rows of clouds {(c0, c1)}, got "
+                             f"{tuple(values.shape)}")
+        mq = int(self.tsizes[c0:c1].max()) if c1 > c0 else 0
+        return interpolate_rows(values, q, s, self.idx[t0:t1], self.d2[t0:t1], mq, n_query=t1 - t0, out=out)
+
+    @torch.no_grad()
+    def labels(self, pred, clouds=None):
+        """The k = 1 label transfer: every target row takes the entry of `pred` (DEVICE ``[source rows of the clouds]``, any
+        dtype) of its NEAREST source point -- a gather by the first neighbour slot.  A target row without a neighbour (an empty
+        source cloud) gets -1."""
+        clouds = (0, len(self)) if clouds is None else clouds
+        c0, c1 = int(clouds[0]), int(clouds[1])
+        q, s, _, (t0, t1), (s0, s1) = self.cloud_range((c0, c1))
+        if pred.dim() != 1 or pred.shape[0] != s1 - s0:
+            raise ValueError(f"Propagator.labels: pred must hold the {s1 - s0} source rows of clouds {(c0, c1)}")
+        if not pred.is_cuda:
+            raise RuntimeError("Propagator.labels: pred must live on the HIP device (there is no CPU path)")
+        sizes = torch.from_numpy(self.tsizes[c0:c1]).to(self.device)
+        base = torch.repeat_interleave(s[:-1], sizes, output_size=t1 - t0)          # first source row of every target row's cloud
+        near = self.idx[t0:t1, 0].long()
+        out = pred[(base + near.clamp(min=0)).clamp(max=max(s1 - s0 - 1, 0))] if s1 > s0 else pred.new_zeros(t1 - t0)
+        return torch.where(near >= 0, out, torch.full_like(out, -1))

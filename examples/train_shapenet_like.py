@@ -53,6 +53,33 @@ def synthetic_split(num_batches, args, seed, device):
     return out
 
 
+def shapenet_sets(root, num_points, full_resolution=False):
+    """-> (trainval set, test set, augmentation).  The training shapes are NormalizeScale + GeodesicFPS(num_points), cached under
+    ``root/processed``.  With `full_resolution` the test shapes keep every point (NormalizeScale alone).  ShapeNet keys its cache
+    by the categories only and writes all splits with the pre_transform of whoever comes first, so the un-subsampled split has a
+    cache of its own, ``root/processed_full``, that the subsampled one cannot shadow."""
+    import deltaconv_amd.transforms as T
+    from deltaconv_amd.datasets import Compose, ShapeNet
+    pre = Compose((T.NormalizeScale(), T.GeodesicFPS(num_points)))                          # train_shapenet.py:30-33
+    aug = Compose((T.RandomScale((2 / 3, 3 / 2)), T.RandomTranslateGlobal(0.2)))            # train_shapenet.py:35-38
+    tr = ShapeNet(root, split="trainval", transform=aug, pre_transform=pre)
+    if full_resolution:
+        te = ShapeNet(root, split="test", pre_transform=T.NormalizeScale(), processed_dir=os.path.join(root, "processed_full"))
+    else:
+        te = ShapeNet(root, split="test", pre_transform=pre)
+    return tr, te, aug
+
+
+def require_full_resolution(sizes, num_points):
+    """Refuse a "full-resolution" store that is the subsampled one under another name: every cloud holding exactly num_points
+    points is what GeodesicFPS(num_points) leaves (a stale or shared cache), and the score on it is the sampled-resolution score."""
+    sizes = [int(n) for n in sizes]
+    if sizes and all(n == num_points for n in sizes):
+        raise SystemExit(f"--eval-full-resolution: every one of the {len(sizes)} test shapes has exactly {num_points} points, the "
+                         "size GeodesicFPS leaves -- this is the subsampled split, not the shapes as read; remove the stale "
+                         "processed_full cache or lower --num_points")
+
+
 def train_epoch(ddp, opt, loader):
     ddp.module.train()
     total, count = 0.0, 0
@@ -99,7 +126,13 @@ def main():
     ap.add_argument("--device-eval", action="store_true",
                     help="with --device-loader: the per-epoch evaluation on the device (deltaconv_amd.DeviceEvaluator: captured "
                          "forward, metrics in one launch per batch, one synchronise per pass) instead of evaluate() below")
+    ap.add_argument("--eval-full-resolution", action="store_true",
+                    help="with --device-eval: keep the test shapes as read (every point, before GeodesicFPS) on the device as well, "
+                         "subsample them there, and report the mean IoU on ALL points of every shape -- the sampled points' vote "
+                         "sums interpolated back by deltaconv_amd.Propagator (k = 3, inference only)")
     args = ap.parse_args()
+    if args.eval_full_resolution and not args.device_eval:
+        raise SystemExit("--eval-full-resolution scores the pre-FPS store through the device evaluator: it needs --device-eval")
     if args.device_eval and not (args.data is not None and args.device_loader):
         raise SystemExit("--device-eval evaluates from a device-resident test set: it needs --data and --device-loader")
 
@@ -117,20 +150,22 @@ def main():
         train = synthetic_split(args.train_batches, args, 1000 * (rank + 1), dev)
         test = synthetic_split(2, args, 777000, dev)
     else:
-        import deltaconv_amd.transforms as T
-        from deltaconv_amd.datasets import Compose, DataLoader, ShapeNet
-        pre = Compose((T.NormalizeScale(), T.GeodesicFPS(args.num_points)))                    # train_shapenet.py:30-33
-        aug = Compose((T.RandomScale((2 / 3, 3 / 2)), T.RandomTranslateGlobal(0.2)))            # train_shapenet.py:35-38
-        tr = ShapeNet(args.data, split="trainval", transform=aug, pre_transform=pre)
-        te = ShapeNet(args.data, split="test", pre_transform=pre)
+        from deltaconv_amd.datasets import DataLoader
+        # --eval-full-resolution: the test shapes keep every point; the subsampling happens on the device below
+        tr, te, aug = shapenet_sets(args.data, args.num_points, args.eval_full_resolution)
     if args.data is not None and args.device_loader:
         # the same recipe, drawn and applied on the device; every rank takes its share of one permutation per epoch
         train = deltaconv.DeviceLoader(deltaconv.DeviceDataset.from_dataset(tr, dev), args.batch_size, shuffle=True,
                                        drop_last=True, transform=aug, seed=1, rank=rank, world=world)
-        test = deltaconv.DeviceLoader(deltaconv.DeviceDataset.from_dataset(te, dev), args.batch_size)
+        test_store = full_store = deltaconv.DeviceDataset.from_dataset(te, dev)
+        if args.eval_full_resolution:        # the pre-FPS store stays; the network sees its geodesic subsample
+            require_full_resolution(full_store.sizes, args.num_points)
+            test_store = full_store.geodesic_subsample(args.num_points, seed=1)
+        test = deltaconv.DeviceLoader(test_store, args.batch_size)
         args.train_batches = len(train)
         if args.device_eval:                 # equal-size clouds (GeodesicFPS to num_points): the full batches replay one graph
-            evaluator = deltaconv.DeviceEvaluator(model, test, task="segmentation")
+            evaluator = deltaconv.DeviceEvaluator(model, test, task="segmentation",
+                                                  propagate_to=full_store if args.eval_full_resolution else None)
     elif args.data is not None:
         sampler = torch.utils.data.distributed.DistributedSampler(tr) if world > 1 else None
 

@@ -760,6 +760,39 @@ int dc_mesh_sample(const float* vert, const int32_t* face, const int64_t* vptr, 
                    float* pos, float* norm, int64_t* y, int32_t* face_id, int64_t* total,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- propagation from a sampled cloud back to its source: two-set kNN and interpolation (csrc/interp.hip, csrc/interp_math.h) -- */
+/* Replaces torch_cluster.knn(x, y, k, batch_x, batch_y) as torch_geometric.nn.knn_interpolate calls it: for each of B cloud
+ * pairs, the k nearest REFERENCE points of every QUERY point.  Inference only (no backward exists).
+ * Order (the contract of dc_knn): fp32 ((dx*dx+dy*dy)+dz*dz) without contraction, ascending, ties by lower reference index.
+ *   query, ref  DEVICE [*,3] fp32 rows
+ *   qptr, rptr  DEVICE [B+1] ABSOLUTE row offsets of the B clouds into query / ref (a slice of a store's offsets serves)
+ *   max_query_cloud  HOST, >= the largest query cloud: it sizes the grid only (queries past it are not searched)
+ *   idx         DEVICE [*,k] int32, row qptr[b] + i: reference ids LOCAL to the pair's reference cloud, -1 = no such neighbour
+ *   d2          DEVICE [*,k] fp32: the value that decided the order, +inf where idx is -1
+ * A reference cloud of fewer than k points (0 included) fills its first slots and pads with -1 / +inf.  A candidate whose
+ * distance is not below +inf -- a NaN coordinate on either side, or an overflow -- is never picked; nothing is indexed out of
+ * the ranges the offsets give.  k outside 1 .. 16, B above 65 535, max_query_cloud outside [0, 2^39) (the grid: at most 2^31 - 1
+ * chunks of 256 queries) or a null pointer: DC_ERR_ARG with a message, checked before anything touches the device; B = 0 or
+ * max_query_cloud = 0 returns DC_OK.  One launch, stream-ordered, no allocation, no
+ * synchronisation, no atomics, capturable: the outputs are a function of the inputs only. */
+int dc_knn_cross(const float* query, const int64_t* qptr, const float* ref, const int64_t* rptr, int32_t B,
+                 int64_t max_query_cloud, int32_t k, int32_t* idx, float* d2, void* stream);
+/* Replaces the arithmetic of torch_geometric.nn.knn_interpolate (PointNet++ feature propagation) on the result of dc_knn_cross:
+ * out[qptr[b] + i, c] = sum_s w_s x[rptr[b] + idx_s, c] / sum_s w_s with w_s = 1.0f / fmaxf(d2_s, 1e-16f) (PyG's clamp), fp32,
+ * slots in order s = 0 .. k-1, every operation rounded on its own, one division per channel (csrc/interp_math.h).  A slot with
+ * idx outside [0, size of the reference cloud) is skipped and indexes nothing; a query with exactly one valid slot gets that row
+ * copied bit for bit (k = 1 is an exact gather), one with no valid slot a row of zeros.  Inference only (no backward exists).
+ *   x           DEVICE [*,ldx] fp32 reference rows, C <= ldx; out DEVICE [*,ldo] fp32, C <= ldo
+ *   qptr, rptr, max_query_cloud, k, idx, d2   as in dc_knn_cross (the same grid: chunks of 256 queries x cloud pairs)
+ * 16-byte loads / stores where the base pointer and the leading dimension allow, scalar otherwise: any C >= 1, the same bits.
+ * k outside 1 .. 16, C outside 1 .. 2^20 (a block counts its 256 queries x C/4 channel groups in 32 bits), ldx or ldo below C, B above
+ * 65 535, max_query_cloud outside [0, 2^39) (the bound of dc_knn_cross: the same grid) or a null pointer: DC_ERR_ARG with a
+ * message, checked before anything touches the device; B = 0 or max_query_cloud = 0 returns DC_OK.  One launch, stream-ordered, no allocation, no synchronisation, no atomics,
+ * capturable. */
+int dc_knn_interpolate(const float* x, int64_t ldx, int32_t C, const int64_t* qptr, const int64_t* rptr, int32_t B,
+                       int64_t max_query_cloud, int32_t k, const int32_t* idx, const float* d2, float* out, int64_t ldo,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
