@@ -13,10 +13,11 @@ import os as _os
 # off; the flag is read when the HIP runtime initialises, so it is defaulted here, at import.
 _os.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")
 
-from . import geometry, nn, models, transforms, datasets, optim, loader, evaluate, meshes, propagate   # noqa: F401
+from . import geometry, nn, models, transforms, datasets, optim, loader, evaluate, meshes, propagate, train   # noqa: F401
 from .data import Batch              # noqa: F401
 from .loader import DeviceDataset, DeviceLoader, RandomJitter   # noqa: F401
 from .evaluate import GraphedEvalStep, DeviceEvaluator   # noqa: F401
+from .train import DeviceTrainer   # noqa: F401
 from .meshes import DeviceMeshDataset   # noqa: F401
 from .propagate import Propagator   # noqa: F401
 

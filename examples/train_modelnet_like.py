@@ -5,7 +5,8 @@ the GPUs of one node.  No dataset ships with this repo (the reference downloads 
 the clouds are synthetic; with `--data <ModelNet40 root>` (raw/<category>/<train|test>/*.off) the reference's
 pipeline runs instead: NormalizeScale -> SamplePoints -> GeodesicFPS once, RandomScale + RandomTranslateGlobal
 per access (train_modelnet.py:29-49), through `deltaconv_amd.datasets`.  `--device-loader` keeps the prepared clouds on
-the GPU; `--device-fps` and `--device-sample` move GeodesicFPS, and SamplePoints with it, there as well.
+the GPU; `--device-fps` and `--device-sample` move GeodesicFPS, and SamplePoints with it, there as well; `--device-train` runs
+the epochs themselves there (deltaconv_amd.DeviceTrainer: captured step, loss and accuracy read once per epoch).
 
     python examples/train_modelnet_like.py --epochs 3
     python examples/train_modelnet_like.py --data /data/ModelNet40 --epochs 50
@@ -66,7 +67,7 @@ def evaluate(model, loader):
     return correct / count
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--batch_size", type=int, default=32)
@@ -91,7 +92,18 @@ def main():
                     help="with --device-loader: SamplePoints and GeodesicFPS leave pre_transform (NormalizeScale alone stays); the "
                          "meshes go to the GPU and are sampled and reduced there, all shapes in a few launches "
                          "(DeviceMeshDataset.sample_points, then DeviceDataset.geodesic_subsample)")
-    args = ap.parse_args()
+    ap.add_argument("--device-train", action="store_true",
+                    help="with --device-loader: the training epoch on the device (deltaconv_amd.DeviceTrainer: the step replayed from "
+                         "one captured graph, loss and accuracy kept on the device, one synchronise per epoch) instead of "
+                         "train_epoch() below; also writes the trainer's state next to last.pt")
+    ap.add_argument("--resume", default=None,
+                    help="with --device-train: continue from the trainer state a run with --device-train wrote (last_trainer.pt; "
+                         "'{rank}' in the name is replaced by the rank)")
+    args = ap.parse_args(argv)
+    if args.device_train and not (args.data is not None and args.device_loader):
+        raise SystemExit("--device-train trains from a device-resident training set: it needs --data and --device-loader")
+    if args.resume is not None and not args.device_train:
+        raise SystemExit("--resume continues from the state of a device trainer: it needs --device-train")
     if args.device_sample and not (args.data is not None and args.device_loader):
         raise SystemExit("--device-sample samples device-resident meshes: it needs --data and --device-loader")
     if args.device_fps and not (args.data is not None and args.device_loader):
@@ -136,6 +148,8 @@ def main():
         args.train_batches = len(train)
         if args.device_eval:                 # equal-size clouds (GeodesicFPS to num_points): the full batches replay one graph
             evaluator = deltaconv.DeviceEvaluator(model, test, task="classification")
+        if args.device_train:                # the capture's warm-up steps leave model and optimizer where they were
+            trainer = deltaconv.DeviceTrainer(model, train, opt, task="classification", reducer=ddp)
     elif args.data is not None:
         sampler = torch.utils.data.distributed.DistributedSampler(tr) if world > 1 else None
         on_dev = lambda loader: (b.to(dev) for b in loader)      # each rank collates and uploads its own shard
@@ -148,13 +162,26 @@ def main():
             def __iter__(self): return on_dev(self.loader)
         train, test = _OnDevice(train_loader), _OnDevice(test_loader)
     os.makedirs(args.logdir, exist_ok=True)
-    for epoch in range(args.epochs):
+    first_epoch = 0
+    trainer_file = "last_trainer.pt" if world == 1 else f"last_trainer.rank{rank}.pt"      # every rank has its own loader share
+    if args.resume is not None:
+        saved = torch.load(args.resume.format(rank=rank), map_location=dev)
+        trainer.load_state_dict(saved["trainer"])
+        sched.load_state_dict(saved["scheduler"])
+        first_epoch = saved["trainer"]["epoch"]
+    for epoch in range(first_epoch, args.epochs):
         t0 = time.perf_counter()
-        loss, acc = train_epoch(ddp, opt, train)
+        if args.device_train:
+            res = trainer.run_epoch(epoch)
+            loss, acc = res["loss"], res["accuracy"]
+        else:
+            loss, acc = train_epoch(ddp, opt, train)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         test_acc = evaluator.run()["accuracy"] if args.device_eval else evaluate(model, test)
         sched.step()
+        if args.device_train:
+            torch.save(dict(trainer=trainer.state_dict(), scheduler=sched.state_dict()), os.path.join(args.logdir, trainer_file))
         if rank == 0:
             print(json.dumps(dict(epoch=epoch, loss=round(loss, 4), train_acc=round(acc, 4), test_acc=round(test_acc, 4),
                                   clouds_per_s=round(world * args.train_batches * args.batch_size / dt, 1))))

@@ -107,7 +107,7 @@ def evaluate(model, loader):
     return float(np.mean(ious))
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--batch_size", type=int, default=16)
@@ -130,7 +130,18 @@ def main():
                     help="with --device-eval: keep the test shapes as read (every point, before GeodesicFPS) on the device as well, "
                          "subsample them there, and report the mean IoU on ALL points of every shape -- the sampled points' vote "
                          "sums interpolated back by deltaconv_amd.Propagator (k = 3, inference only)")
-    args = ap.parse_args()
+    ap.add_argument("--device-train", action="store_true",
+                    help="with --device-loader: the training epoch on the device (deltaconv_amd.DeviceTrainer: the step replayed from "
+                         "one captured graph, loss and the part IoU of the training forward kept on the device, one synchronise per "
+                         "epoch) instead of train_epoch() below; prints train_miou and writes the trainer's state next to last.pt")
+    ap.add_argument("--resume", default=None,
+                    help="with --device-train: continue from the trainer state a run with --device-train wrote (last_trainer.pt; "
+                         "'{rank}' in the name is replaced by the rank)")
+    args = ap.parse_args(argv)
+    if args.device_train and not (args.data is not None and args.device_loader):
+        raise SystemExit("--device-train trains from a device-resident training set: it needs --data and --device-loader")
+    if args.resume is not None and not args.device_train:
+        raise SystemExit("--resume continues from the state of a device trainer: it needs --device-train")
     if args.eval_full_resolution and not args.device_eval:
         raise SystemExit("--eval-full-resolution scores the pre-FPS store through the device evaluator: it needs --device-eval")
     if args.device_eval and not (args.data is not None and args.device_loader):
@@ -166,6 +177,8 @@ def main():
         if args.device_eval:                 # equal-size clouds (GeodesicFPS to num_points): the full batches replay one graph
             evaluator = deltaconv.DeviceEvaluator(model, test, task="segmentation",
                                                   propagate_to=full_store if args.eval_full_resolution else None)
+        if args.device_train:                # the capture's warm-up steps leave model and optimizer where they were
+            trainer = deltaconv.DeviceTrainer(model, train, opt, task="segmentation", reducer=ddp)
     elif args.data is not None:
         sampler = torch.utils.data.distributed.DistributedSampler(tr) if world > 1 else None
 
@@ -179,15 +192,29 @@ def main():
         test = _OnDevice(DataLoader(te, batch_size=args.batch_size, shuffle=False, drop_last=False))
         args.train_batches = len(train.loader)
     os.makedirs(args.logdir, exist_ok=True)
-    for epoch in range(args.epochs):
+    first_epoch = 0
+    trainer_file = "last_trainer.pt" if world == 1 else f"last_trainer.rank{rank}.pt"      # every rank has its own loader share
+    if args.resume is not None:
+        saved = torch.load(args.resume.format(rank=rank), map_location=dev)
+        trainer.load_state_dict(saved["trainer"])
+        sched.load_state_dict(saved["scheduler"])
+        first_epoch = saved["trainer"]["epoch"]
+    for epoch in range(first_epoch, args.epochs):
         t0 = time.perf_counter()
-        loss = train_epoch(ddp, opt, train)
+        if args.device_train:
+            res = trainer.run_epoch(epoch)
+            loss = res["loss"]
+        else:
+            loss = train_epoch(ddp, opt, train)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         miou = evaluator.run()["mean_iou"] if args.device_eval else evaluate(model, test)
         sched.step()
+        if args.device_train:
+            torch.save(dict(trainer=trainer.state_dict(), scheduler=sched.state_dict()), os.path.join(args.logdir, trainer_file))
         if rank == 0:
-            print(json.dumps(dict(epoch=epoch, loss=round(loss, 4), test_mean_iou=round(miou, 4),
+            train_miou = dict(train_miou=round(res["mean_iou"], 4)) if args.device_train else {}    # of the training forward
+            print(json.dumps(dict(epoch=epoch, loss=round(loss, 4), **train_miou, test_mean_iou=round(miou, 4),
                                   clouds_per_s=round(world * args.train_batches * args.batch_size / dt, 1))))
             torch.save(model.state_dict(), os.path.join(args.logdir, "last.pt"))   # reference key names
     if world > 1:
