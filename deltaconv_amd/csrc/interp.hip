@@ -1,6 +1,7 @@
 // Two-set nearest-neighbour search and inverse-squared-distance interpolation, batched over cloud pairs -- replaces
 // torch_cluster.knn(x, y, k, batch_x, batch_y) and torch_geometric.nn.knn_interpolate (PointNet++ feature propagation): the way
-// back up from a sampled cloud to the points or vertices it was sampled from.  Inference only: no backward kernel.
+// back up from a sampled cloud to the points or vertices it was sampled from -- and the gradient of the interpolation w.r.t. the
+// interpolated FEATURES (dc_knn_cross_transpose + dc_knn_interpolate_backward).  No gradient for positions or distances.
 //
 // Order (bit-exact contract shared with dc_knn, knn.hip:5-6): fp32 squared distance ((dx*dx + dy*dy) + dz*dz) evaluated WITHOUT
 // fma contraction, ascending, ties by lower reference index.  The arithmetic is csrc/interp_math.h (shared with
@@ -14,6 +15,20 @@
 //   interpolate_kernel  thread = (query, group of 4 channels), consecutive threads on consecutive groups of one query: the k
 //                       reference rows are read 16 bytes at a time where x, ldx and C allow, scalar otherwise (any C >= 1).
 // Plain vector loads and stores, no atomics: the outputs are a function of the inputs only.
+//
+// The backward (csrc/interp_math.h: coef / pick / bwd4) is a transposed, ordered sum -- no floating-point atomics anywhere:
+//   transpose_*_kernel   the in-edge lists of every reference row, the shape of csc.hip: count (integer atomics, one thread per
+//                        slot), exclusive scan over ALL reference rows of the call (per-1024-row sums, then every block adds the
+//                        sums before it: the base of a pair is the valid slots of the earlier pairs), unordered fill (integer
+//                        cursors), then the ranking: ONE FILL POSITION PER THREAD -- it finds its list through idx[e] and counts
+//                        the smaller entries of that list.  A list here can hold thousands of entries (a 200 k-vertex mesh
+//                        against 1024 samples: ~600 a row; a one-point cloud: every query), so the L^2 comparisons of a long list
+//                        are spread over the grid, L a thread, instead of one list per wave as csc_rank_kernel does.  The lists
+//                        come out in ascending edge id whatever order the atomics ran in: a function of the inputs only.
+//   interpolate_backward_kernel   thread = (reference row, group of 4 channels) on the grid (chunks of 256 / (C/4) reference rows
+//                        up to max_ref_cloud: about one item a thread) x (cloud pairs); it walks the row's in-edges in order,
+//                        four loads in flight, and reads g 16 bytes at a time where g, ldg and C allow, scalar otherwise.
+//                        Gather-bound, the cost of a thread is its list length.
 #include "common.h"
 #include "interp_math.h"
 
@@ -105,6 +120,148 @@ __global__ __launch_bounds__(IT_THREADS) void interpolate_kernel(const float* __
     }
 }
 
+// ---- backward: transposed lists -----------------------------------------------------------------------------------------------
+typedef unsigned long long u64;
+constexpr int SC_THREADS = 1024;              // reference rows of a scan block
+
+__device__ __forceinline__ u64 block_sum(u64 v, u64* red) {          // red [SC_THREADS / 64]; every thread gets the sum
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    u64 s = 0;
+#pragma unroll
+    for (int w = 0; w < SC_THREADS / 64; ++w) s += red[w];
+    __syncthreads();
+    return s;
+}
+
+__global__ __launch_bounds__(IT_THREADS) void transpose_count_kernel(const int64_t* __restrict__ qptr,
+                                                                     const int64_t* __restrict__ rptr, int B, int k,
+                                                                     const int32_t* __restrict__ idx, long long ne,
+                                                                     long long num_ref, u64* __restrict__ cnt) {
+    const long long e = (long long)blockIdx.x * IT_THREADS + threadIdx.x;
+    if (e >= ne) return;
+    const long long r = dcinterp::pick(qptr, rptr, B, k, idx, e);
+    if (r >= 0 && r < num_ref) atomicAdd(cnt + r, 1ull);
+}
+
+__global__ __launch_bounds__(SC_THREADS) void transpose_sum_kernel(const u64* __restrict__ cnt, long long num_ref,
+                                                                   u64* __restrict__ part) {
+    __shared__ u64 red[SC_THREADS / 64];
+    const long long r = (long long)blockIdx.x * SC_THREADS + threadIdx.x;
+    const u64 s = block_sum(r < num_ref ? cnt[r] : 0ull, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// exclusive scan of cnt: tptr and the fill cursors (the cursors replace cnt)
+__global__ __launch_bounds__(SC_THREADS) void transpose_scan_kernel(u64* __restrict__ cnt, long long num_ref,
+                                                                    const u64* __restrict__ part, int64_t* __restrict__ tptr) {
+    __shared__ u64 red[SC_THREADS / 64];
+    __shared__ u64 sc[SC_THREADS];
+    const int tid = threadIdx.x;
+    u64 before = 0;
+    for (int i = tid; i < (int)blockIdx.x; i += SC_THREADS) before += part[i];
+    const u64 base = block_sum(before, red);
+    const long long r = (long long)blockIdx.x * SC_THREADS + tid;
+    const u64 c = r < num_ref ? cnt[r] : 0ull;
+    sc[tid] = c;
+    __syncthreads();
+    for (int off = 1; off < SC_THREADS; off <<= 1) {      // inclusive Hillis-Steele scan
+        const u64 v = tid >= off ? sc[tid - off] : 0ull;
+        __syncthreads();
+        sc[tid] += v;
+        __syncthreads();
+    }
+    if (r < num_ref) {
+        const u64 excl = base + sc[tid] - c;
+        tptr[r] = (int64_t)excl;
+        cnt[r] = excl;
+        if (r == num_ref - 1) tptr[num_ref] = (int64_t)(excl + c);
+    }
+}
+
+__global__ __launch_bounds__(IT_THREADS) void transpose_fill_kernel(const int64_t* __restrict__ qptr,
+                                                                    const int64_t* __restrict__ rptr, int B, int k,
+                                                                    const int32_t* __restrict__ idx, long long ne,
+                                                                    long long num_ref, u64* __restrict__ cursor,
+                                                                    int64_t* __restrict__ unordered) {
+    const long long e = (long long)blockIdx.x * IT_THREADS + threadIdx.x;
+    if (e >= ne) return;
+    const long long r = dcinterp::pick(qptr, rptr, B, k, idx, e);
+    if (r < 0 || r >= num_ref) return;
+    const u64 at = atomicAdd(cursor + r, 1ull);
+    if (at < (u64)ne) unordered[at] = e;      // (always: the counts came from the same inputs)
+}
+
+__global__ __launch_bounds__(IT_THREADS) void transpose_rank_kernel(const int64_t* __restrict__ qptr,
+                                                                    const int64_t* __restrict__ rptr, int B, int k,
+                                                                    const int32_t* __restrict__ idx, const float* __restrict__ d2,
+                                                                    long long ne, long long num_ref,
+                                                                    const int64_t* __restrict__ tptr,
+                                                                    const int64_t* __restrict__ unordered,
+                                                                    int64_t* __restrict__ tedge, float* __restrict__ tcoef) {
+    const long long t = (long long)blockIdx.x * IT_THREADS + threadIdx.x;
+    if (t >= ne || t >= tptr[num_ref]) return;
+    const long long e = unordered[t];
+    if (e < 0 || e >= ne) return;
+    const long long q = e / k;
+    const int s = (int)(e - q * k);
+    const int b = dcinterp::pair_of(qptr, B, q);
+    if (b < 0) return;
+    const long long rbase = rptr[b], nr = rptr[b + 1] - rbase, j = idx[e];
+    if (!dcinterp::valid_slot(j, nr) || rbase + j >= num_ref) return;
+    long long lo = tptr[rbase + j], hi = tptr[rbase + j + 1];
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > ne ? ne : hi;
+    long long rank = 0;
+#pragma unroll 8
+    for (long long p = lo; p < hi; ++p) rank += unordered[p] < e;
+    if (lo + rank >= hi) return;              // (never: e is one of the list's distinct entries)
+    tedge[lo + rank] = e;
+    tcoef[lo + rank] = dcinterp::coef(nr, k, idx + q * k, d2 + q * k, s);
+}
+
+__global__ __launch_bounds__(IT_THREADS) void interpolate_backward_kernel(const float* __restrict__ g, long long ldg,
+                                                                          long long g_rows, int C,
+                                                                          const int64_t* __restrict__ rptr, int k,
+                                                                          const int64_t* __restrict__ tptr,
+                                                                          const int64_t* __restrict__ tedge,
+                                                                          const float* __restrict__ tcoef, long long num_edges,
+                                                                          long long edge_base, float* __restrict__ dx,
+                                                                          long long ldx, int rpb, int vec_in, int vec_out) {
+    const int b = blockIdx.y;
+    const long long rbase = rptr[b], nr = rptr[b + 1] - rbase;
+    const long long r0 = (long long)blockIdx.x * rpb;
+    if (r0 >= nr) return;                     // block-uniform (covers nr <= 0)
+    const int rows = (int)(nr - r0 < rpb ? nr - r0 : rpb);
+    const int groups = (C + 3) >> 2;
+    for (int item = threadIdx.x; item < rows * groups; item += IT_THREADS) {
+        const int r = item / groups, gi = item - r * groups;
+        const long long row = rbase + r0 + r;
+        const int c0 = 4 * gi, nc = C - c0 < 4 ? C - c0 : 4;
+        long long lo = tptr[row], hi = tptr[row + 1];
+        lo = lo < 0 ? 0 : lo;
+        hi = hi > num_edges ? num_edges : hi;
+        float v[4];
+        dcinterp::bwd4(g, ldg, g_rows, k, edge_base, tedge + lo, tcoef + lo, hi > lo ? hi - lo : 0, c0, nc, vec_in && nc == 4, v);
+        float* o = dx + row * ldx + c0;
+        if (vec_out && nc == 4) {
+            dc_f32x4 t = {v[0], v[1], v[2], v[3]};
+            *reinterpret_cast<dc_f32x4*>(o) = t;
+        } else {
+            for (int c = 0; c < nc; ++c) o[c] = v[c];
+        }
+    }
+}
+
+constexpr long long TR_MAX_EDGES = (1ll << 31) * IT_THREADS - IT_THREADS;     // one thread per slot: at most 2^31 - 1 blocks
+constexpr long long TR_MAX_REF = (1ll << 31) * SC_THREADS - SC_THREADS;
+
+size_t transpose_bytes(long long num_query, long long num_ref, int k) {
+    return 8 * ((size_t)num_ref + (size_t)dc_cdiv(num_ref, SC_THREADS) + (size_t)num_query * (size_t)k);
+}
+
 template <int K>
 int launch_cross(const float* query, const int64_t* qptr, const float* ref, const int64_t* rptr, int B, long long max_q, int k,
                  int32_t* idx, float* d2, hipStream_t s) {
@@ -149,5 +306,78 @@ DC_EXPORT int dc_knn_interpolate(const float* x, int64_t ldx, int32_t C, const i
                        static_cast<hipStream_t>(stream), x, (long long)ldx, (int)C, qptr, rptr, (int)k, idx, d2, out, (long long)ldo,
                        vec_in, vec_out);
     DC_CHECK_LAUNCH("dc_knn_interpolate");
+    return DC_OK;
+}
+
+// workspace: the counters / fill cursors [num_ref], the scan's block sums and the unordered fill [num_query * k], 8 bytes each
+DC_EXPORT size_t dc_knn_cross_transpose_workspace_bytes(int64_t num_query, int64_t num_ref, int32_t k) {
+    if (num_query < 0 || num_ref < 0 || k < 1 || k > dcinterp::MAX_K || num_query * k > TR_MAX_EDGES || num_ref > TR_MAX_REF)
+        return 0;
+    return transpose_bytes(num_query, num_ref, k);
+}
+
+DC_EXPORT int dc_knn_cross_transpose(const int64_t* qptr, const int64_t* rptr, int32_t B, int64_t num_query, int64_t num_ref,
+                                     int32_t k, const int32_t* idx, const float* d2, int64_t* tptr, int64_t* tedge, float* tcoef,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+    DC_REQUIRE(B >= 0, "dc_knn_cross_transpose: B = %d cloud pairs", B);
+    DC_REQUIRE(k >= 1 && k <= dcinterp::MAX_K, "dc_knn_cross_transpose: k = %d outside [1, %d]", k, dcinterp::MAX_K);
+    DC_REQUIRE(num_query >= 0 && num_query * k <= TR_MAX_EDGES, "dc_knn_cross_transpose: num_query = %lld: num_query * k outside [0, 2^39)",
+               (long long)num_query);
+    DC_REQUIRE(num_ref >= 0 && num_ref <= TR_MAX_REF, "dc_knn_cross_transpose: num_ref = %lld outside [0, 2^41)", (long long)num_ref);
+    DC_REQUIRE(tptr, "dc_knn_cross_transpose: null pointer (tptr)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long long ne = (long long)num_query * k;
+    if (B == 0 || ne == 0 || num_ref == 0) {  // no in-edge at all: every list is empty
+        dc_zero_words(tptr, 2 * ((long)num_ref + 1), s);
+        DC_CHECK_LAUNCH("dc_knn_cross_transpose");
+        return DC_OK;
+    }
+    DC_REQUIRE(qptr && rptr && idx && d2 && tedge && tcoef, "dc_knn_cross_transpose: null pointer (qptr, rptr, idx, d2, tedge, tcoef)");
+    DC_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0 && workspace_bytes >= transpose_bytes(num_query, num_ref, k),
+               "dc_knn_cross_transpose: workspace null, not 8-byte aligned or too small (%zu bytes, needs %zu)", workspace_bytes,
+               transpose_bytes(num_query, num_ref, k));
+    const int sblocks = dc_cdiv(num_ref, SC_THREADS), eblocks = dc_cdiv(ne, IT_THREADS);
+    u64* cnt = static_cast<u64*>(workspace);
+    u64* part = cnt + num_ref;
+    int64_t* unordered = reinterpret_cast<int64_t*>(part + sblocks);
+    dc_zero_words(cnt, 2 * (long)num_ref, s);
+    hipLaunchKernelGGL(transpose_count_kernel, dim3(eblocks), dim3(IT_THREADS), 0, s, qptr, rptr, (int)B, (int)k, idx, ne,
+                       (long long)num_ref, cnt);
+    hipLaunchKernelGGL(transpose_sum_kernel, dim3(sblocks), dim3(SC_THREADS), 0, s, cnt, (long long)num_ref, part);
+    hipLaunchKernelGGL(transpose_scan_kernel, dim3(sblocks), dim3(SC_THREADS), 0, s, cnt, (long long)num_ref, part, tptr);
+    hipLaunchKernelGGL(transpose_fill_kernel, dim3(eblocks), dim3(IT_THREADS), 0, s, qptr, rptr, (int)B, (int)k, idx, ne,
+                       (long long)num_ref, cnt, unordered);
+    hipLaunchKernelGGL(transpose_rank_kernel, dim3(eblocks), dim3(IT_THREADS), 0, s, qptr, rptr, (int)B, (int)k, idx, d2, ne,
+                       (long long)num_ref, tptr, unordered, tedge, tcoef);
+    DC_CHECK_LAUNCH("dc_knn_cross_transpose");
+    return DC_OK;
+}
+
+DC_EXPORT int dc_knn_interpolate_backward(const float* g, int64_t ldg, int64_t num_g_rows, int32_t C, const int64_t* rptr, int32_t B,
+                                          int64_t max_ref_cloud, int32_t k, const int64_t* tptr, const int64_t* tedge,
+                                          const float* tcoef, int64_t num_edges, int64_t edge_base, float* dx, int64_t ldx,
+                                          void* stream) {
+    DC_REQUIRE(B >= 0 && B <= 65535, "dc_knn_interpolate_backward: B = %d cloud pairs, supported: 0 .. 65535 per launch", B);
+    DC_REQUIRE(k >= 1 && k <= dcinterp::MAX_K, "dc_knn_interpolate_backward: k = %d outside [1, %d]", k, dcinterp::MAX_K);
+    DC_REQUIRE(C >= 1 && C <= (1 << 20), "dc_knn_interpolate_backward: C = %d channels, supported: 1 .. 2^20", C);
+    DC_REQUIRE(ldg >= C && ldx >= C, "dc_knn_interpolate_backward: leading dimensions ldg = %lld, ldx = %lld below C = %d",
+               (long long)ldg, (long long)ldx, C);
+    DC_REQUIRE(max_ref_cloud >= 0 && max_ref_cloud < (1ll << 31),
+               "dc_knn_interpolate_backward: max_ref_cloud = %lld outside [0, 2^31)", (long long)max_ref_cloud);
+    DC_REQUIRE(num_g_rows >= 0 && num_edges >= 0, "dc_knn_interpolate_backward: num_g_rows = %lld, num_edges = %lld below 0",
+               (long long)num_g_rows, (long long)num_edges);
+    if (B == 0 || max_ref_cloud == 0) return DC_OK;
+    DC_REQUIRE(rptr && tptr && dx, "dc_knn_interpolate_backward: null pointer (rptr, tptr, dx)");
+    DC_REQUIRE((num_edges == 0 || num_g_rows == 0) || (g && tedge && tcoef),
+               "dc_knn_interpolate_backward: null pointer (g, tedge, tcoef)");
+    if (!g || !tedge || !tcoef) num_edges = 0;                   // nothing to read: every list is cut to nothing, dx gets zeros
+    const int vec_in = (reinterpret_cast<uintptr_t>(g) & 15) == 0 && (ldg & 3) == 0;
+    const int vec_out = (reinterpret_cast<uintptr_t>(dx) & 15) == 0 && (ldx & 3) == 0;
+    // a thread's cost is its list length, so a workgroup takes only as many reference rows as give each thread about one item
+    const int groups = (C + 3) >> 2, rpb = groups >= IT_THREADS ? 1 : IT_THREADS / groups;
+    hipLaunchKernelGGL(interpolate_backward_kernel, dim3(dc_cdiv(max_ref_cloud, rpb), B), dim3(IT_THREADS), 0,
+                       static_cast<hipStream_t>(stream), g, (long long)ldg, (long long)num_g_rows, (int)C, rptr, (int)k, tptr, tedge,
+                       tcoef, (long long)num_edges, (long long)edge_base, dx, (long long)ldx, rpb, vec_in, vec_out);
+    DC_CHECK_LAUNCH("dc_knn_interpolate_backward");
     return DC_OK;
 }

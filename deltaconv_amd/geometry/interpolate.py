@@ -3,10 +3,14 @@
 do -- the way back up from a sampled cloud to the points or vertices it was sampled from.  ``deltaconv_amd.Propagator``
 (propagate.py) is the dataset-level form.
 
-Inference only: nothing here is recorded by autograd and there is no backward kernel.  There is no CPU path."""
+The gradient w.r.t. the interpolated FEATURES is opt-in (``knn_interpolate(..., differentiable=True)``): the transposed lists of
+the search (``knn_cross_transpose``: ``dc_knn_cross_transpose``) and an ordered, atomics-free sum over them
+(``interpolate_rows_backward``: ``dc_knn_interpolate_backward``), bit-reproducible.  There is NO gradient for positions or
+distances (PyG's op is differentiable through the weights; this one is not).  There is no CPU path."""
 import torch
+from torch.autograd.function import once_differentiable
 
-__all__ = ["knn_cross", "knn_interpolate", "interpolate_rows", "MAX_K"]
+__all__ = ["knn_cross", "knn_cross_transpose", "knn_interpolate", "interpolate_rows", "interpolate_rows_backward", "MAX_K"]
 
 MAX_K = 16                 # csrc/interp_math.h: MAX_K
 MAX_PAIRS = 65535          # cloud pairs per launch (the grid's second dimension)
@@ -70,7 +74,7 @@ def knn_cross(pos_query, pos_ref, k, ptr_query=None, ptr_ref=None, batch_query=N
     -> ``(idx int32 [Nq,k], d2 fp32 [Nq,k])``: reference ids LOCAL to the pair's reference cloud in ascending fp32 squared
     distance, ties by the lower id (the order contract of ``knn_graph``); ``-1`` / ``+inf`` where a reference cloud has fewer
     than k points.  A point with a NaN coordinate is never picked.  Rows of ``pos_query`` outside every cloud keep what the
-    buffers held (``-1`` / ``+inf`` when allocated here).  Inference only: the result carries no autograd graph."""
+    buffers held (``-1`` / ``+inf`` when allocated here).  The result carries no autograd graph: positions are not differentiated."""
     from .._lib import lib
     pos_query, pos_ref = _device_f32("knn_cross: pos_query", pos_query, 3), _device_f32("knn_cross: pos_ref", pos_ref, 3)
     k = int(k)
@@ -98,7 +102,8 @@ def knn_cross(pos_query, pos_ref, k, ptr_query=None, ptr_ref=None, batch_query=N
 def interpolate_rows(x, qptr, rptr, idx, d2, max_query_cloud, n_query=None, out=None):
     """The arithmetic half of ``knn_interpolate`` on a search result: x [Nr,C] DEVICE fp32 (rows may be strided) -> [n_query,C]
     with row ``qptr[b] + i`` = the inverse-squared-distance mean of rows ``rptr[b] + idx[qptr[b] + i]`` of x
-    (csrc/interp_math.h: ``w = 1 / max(d2, 1e-16)``; one valid slot is an exact copy, none a row of zeros).  Inference only."""
+    (csrc/interp_math.h: ``w = 1 / max(d2, 1e-16)``; one valid slot is an exact copy, none a row of zeros).  Not recorded by
+    autograd; ``interpolate_rows_backward`` is its gradient w.r.t. x."""
     from .._lib import lib
     if not torch.is_tensor(x) or not x.is_cuda:
         raise RuntimeError("interpolate_rows: x must be a tensor on a HIP device (there is no CPU path)")
@@ -129,16 +134,117 @@ def interpolate_rows(x, qptr, rptr, idx, d2, max_query_cloud, n_query=None, out=
     return out
 
 
-def knn_interpolate(x, pos_x, pos_y, batch_x=None, batch_y=None, k=3, ptr_x=None, ptr_y=None):
+def knn_cross_transpose(idx, d2, qptr, rptr, num_ref=None):
+    """The transposed lists of a ``knn_cross`` result (``dc_knn_cross_transpose``): for every reference row its in-edges, i.e. the
+    valid slots ``(q, s)`` that picked it, as edge ids ``e = q * k + s`` (q: the row of ``idx``) in ASCENDING order, with the
+    coefficient of each (csrc/interp_math.h: 1 for the only valid slot of a query, else ``w_s / den``).
+
+    idx int32 / d2 fp32 ``[Nq,k]`` on the DEVICE, qptr / rptr int64 ``[B+1]`` ABSOLUTE offsets (any B).  ``num_ref``: the rows of
+    the reference tensor (``tptr`` is indexed like it); where it is not given it is read from ``rptr[-1]`` (one synchronise).
+    -> ``(tptr int64 [num_ref+1], tedge int64 [Nq*k], tcoef fp32 [Nq*k])``: the list of row r is ``[tptr[r], tptr[r+1])``; the
+    first ``tptr[-1]`` entries of tedge / tcoef are written, the rest is zero.  A function of the inputs only (integer atomics,
+    then a ranking pass); no synchronise with ``num_ref`` given, capturable.  No gradient flows into ``d2``."""
+    from .._lib import lib
+    for name, t, dt in (("idx", idx, torch.int32), ("d2", d2, torch.float32)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError(f"knn_cross_transpose: {name} must be a tensor on a HIP device (there is no CPU path)")
+        if t.dtype != dt or t.dim() != 2 or not t.is_contiguous():
+            raise ValueError(f"knn_cross_transpose: {name} must be contiguous {dt} [Nq, k]")
+    if idx.shape != d2.shape or not 1 <= idx.shape[1] <= MAX_K:
+        raise ValueError(f"knn_cross_transpose: idx {tuple(idx.shape)} and d2 {tuple(d2.shape)} must agree, k in [1, {MAX_K}]")
+    dev = idx.device
+    qptr = torch.as_tensor(qptr).to(device=dev, dtype=torch.int64).contiguous()
+    rptr = torch.as_tensor(rptr).to(device=dev, dtype=torch.int64).contiguous()
+    if qptr.dim() != 1 or qptr.shape != rptr.shape or qptr.numel() < 1:
+        raise ValueError("knn_cross_transpose: qptr and rptr must hold B+1 offsets each")
+    nq, k = int(idx.shape[0]), int(idx.shape[1])
+    num_ref = int(rptr[-1]) if num_ref is None else int(num_ref)
+    with torch.no_grad():
+        tptr = torch.empty(num_ref + 1, dtype=torch.int64, device=dev)
+        tedge = torch.zeros(nq * k, dtype=torch.int64, device=dev)
+        tcoef = torch.zeros(nq * k, dtype=torch.float32, device=dev)
+        nbytes = int(lib.raw("dc_knn_cross_transpose_workspace_bytes")(nq, num_ref, k))
+        work = torch.empty(max(nbytes, 8) // 8, dtype=torch.int64, device=dev)
+        lib.call("dc_knn_cross_transpose", qptr, rptr, int(qptr.numel()) - 1, nq, num_ref, k, idx, d2, tptr, tedge, tcoef, work,
+                 work.numel() * 8)
+    return tptr, tedge, tcoef
+
+
+def interpolate_rows_backward(g, rptr, tptr, tedge, tcoef, k, max_ref_cloud, n_ref=None, edge_base=0, out=None):
+    """The gradient of ``interpolate_rows`` w.r.t. x on the lists of ``knn_cross_transpose`` (``dc_knn_interpolate_backward``):
+    g ``[n_query,C]`` DEVICE fp32 (rows may be strided) -> fp32 ``[n_ref,C]`` with
+    ``dx[r] = sum over the in-edges of r, in ascending order, of tcoef * g[e // k - edge_base]``, every product and sum rounded on
+    its own: no atomics, the same bits on every run.  Every reference row of every pair is written (zeros without in-edges); rows
+    of ``out`` outside every pair keep what they held (zeros when allocated here).  ``tptr`` is indexed by the rows ``rptr``
+    names; ``edge_base``: see ``dc_knn_interpolate_backward``.  One launch per 65 535 pairs, no synchronise."""
+    from .._lib import lib
+    if not torch.is_tensor(g) or not g.is_cuda:
+        raise RuntimeError("interpolate_rows_backward: g must be a tensor on a HIP device (there is no CPU path)")
+    if g.dim() != 2 or g.shape[1] < 1:
+        raise ValueError(f"interpolate_rows_backward: g must be [n, C] with C >= 1, got {tuple(g.shape)}")
+    if g.dtype != torch.float32 or (g.shape[1] > 1 and g.stride(1) != 1) or (g.shape[0] > 1 and g.stride(0) < g.shape[1]):
+        g = g.float().contiguous()
+    c, k = int(g.shape[1]), int(k)
+    ldg = int(g.stride(0)) if g.shape[0] > 1 else c
+    n_ref = int(tptr.numel()) - 1 if n_ref is None else int(n_ref)
+    if out is None:
+        out = torch.zeros((n_ref, c), dtype=torch.float32, device=g.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n_ref, c) or (c > 1 and out.stride(1) != 1) or \
+            (n_ref > 1 and out.stride(0) < c):
+        raise ValueError(f"interpolate_rows_backward: out must be float32 [{n_ref}, {c}] with unit stride along the channels and "
+                         "rows that do not overlap")
+    ldo = int(out.stride(0)) if n_ref > 1 else c
+    b = int(rptr.numel()) - 1
+    if n_ref == 0:
+        return out
+    if g.shape[0] == 0:                        # no query row at all: every edge is skipped, a row that is never read stands in
+        g = g.new_zeros((1, c))
+    for lo, hi in _launches(b):
+        lib.call("dc_knn_interpolate_backward", g, ldg, int(g.shape[0]), c, rptr[lo:hi + 1], hi - lo, int(max_ref_cloud), k, tptr,
+                 tedge, tcoef, int(tedge.numel()), int(edge_base), out, ldo)
+    return out
+
+
+class _InterpolateRows(torch.autograd.Function):
+    """``interpolate_rows`` on the autograd graph: the forward is the inference kernel (the same bits), the backward ONE launch on
+    transposed lists built beforehand.  ``covered``: every row of x lies in a pair, so the backward writes all of dx itself."""
+
+    @staticmethod
+    def forward(ctx, x, qptr, rptr, idx, d2, tptr, tedge, tcoef, mq, mr, n_query, edge_base, covered):
+        ctx.save_for_backward(rptr, tptr, tedge, tcoef)
+        ctx.meta = (tuple(x.shape), x.dtype, int(idx.shape[1]), int(mr), int(edge_base), bool(covered))
+        return interpolate_rows(x.detach(), qptr, rptr, idx, d2, mq, n_query=n_query)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        rptr, tptr, tedge, tcoef = ctx.saved_tensors
+        shape, dtype, k, mr, edge_base, covered = ctx.meta
+        out = torch.empty(shape, dtype=torch.float32, device=g.device) if covered else None
+        dx = interpolate_rows_backward(g, rptr, tptr, tedge, tcoef, k, mr, n_ref=shape[0], edge_base=edge_base, out=out)
+        return (dx.to(dtype),) + (None,) * 12
+
+
+def knn_interpolate(x, pos_x, pos_y, batch_x=None, batch_y=None, k=3, ptr_x=None, ptr_y=None, differentiable=False,
+                    max_query_cloud=None, max_ref_cloud=None):
     """``torch_geometric.nn.knn_interpolate(x, pos_x, pos_y, batch_x, batch_y, k)``: the features ``x [len(pos_x), C]`` at
     ``pos_x`` interpolated to ``pos_y`` -- for every target its k nearest sources (of the same cloud), weighted by
     ``1 / clamp(d^2, min=1e-16)``.  -> fp32 ``[len(pos_y), C]``.  ``ptr_x`` / ``ptr_y`` (int64 [B+1] row offsets) stand in for
     the sorted ``batch`` vectors where the offsets are at hand.
 
-    INFERENCE ONLY: there is no backward kernel.  ``x.requires_grad`` while grad mode is on raises ``RuntimeError`` instead of
-    cutting the graph silently -- call it under ``torch.no_grad()`` or pass ``x.detach()``.  Non-HIP tensors raise: there is no
-    CPU path."""
-    if torch.is_tensor(x) and x.requires_grad and torch.is_grad_enabled():
+    ``differentiable=False`` (the default) is INFERENCE ONLY: ``x.requires_grad`` while grad mode is on raises ``RuntimeError``
+    instead of cutting the graph silently -- call it under ``torch.no_grad()``, pass ``x.detach()``, or ask for the gradient:
+
+    ``differentiable=True``: an ``x`` that requires grad gives a result on the autograd graph (the same forward bits).  The
+    forward also builds the transposed lists of the search (``knn_cross_transpose``), so that the backward is one launch of an
+    ordered sum: no floating-point atomics, the same gradient bits on every run; it is a contiguous fp32-computed tensor of x's
+    shape, also for a strided or 1-D x.  Once differentiable; NO gradient for ``pos_x`` / ``pos_y`` (PyG's op has one through the
+    weights).  ``max_query_cloud`` / ``max_ref_cloud``: the largest target / source cloud where the host knows them; with both
+    and ``ptr_x`` / ``ptr_y`` given nothing synchronises and forward + backward can be captured in a ``torch.cuda.graph``.
+
+    Non-HIP tensors raise: there is no CPU path."""
+    needs_grad = torch.is_tensor(x) and x.requires_grad and torch.is_grad_enabled()
+    if needs_grad and not differentiable:
         raise RuntimeError("knn_interpolate: x requires grad, but the device interpolation is inference-only (no backward kernel); "
                            "call it under torch.no_grad() or pass x.detach()")
     if not torch.is_tensor(x) or not x.is_cuda:
@@ -149,6 +255,11 @@ def knn_interpolate(x, pos_x, pos_y, batch_x=None, batch_y=None, k=3, ptr_x=None
     if x.dim() != 2 or x.shape[0] != pos_x.shape[0]:
         raise ValueError(f"knn_interpolate: x must hold one row per point of pos_x, got {tuple(x.shape)} for {pos_x.shape[0]} points")
     with torch.no_grad():
-        qptr, rptr, b, mq = _pairs(pos_y, pos_x, ptr_y, ptr_x, batch_y, batch_x, "knn_interpolate")
+        qptr, rptr, b, mq = _pairs(pos_y, pos_x, ptr_y, ptr_x, batch_y, batch_x, "knn_interpolate", max_query_cloud)
         idx, d2 = knn_cross(pos_y, pos_x, k, ptr_query=qptr, ptr_ref=rptr, max_query_cloud=mq)
-        return interpolate_rows(x.detach(), qptr, rptr, idx, d2, mq, n_query=pos_y.shape[0])
+        if not needs_grad:
+            return interpolate_rows(x.detach(), qptr, rptr, idx, d2, mq, n_query=pos_y.shape[0])
+        mr = int(max_ref_cloud) if max_ref_cloud is not None else (int((rptr[1:] - rptr[:-1]).max()) if b else 0)
+        tptr, tedge, tcoef = knn_cross_transpose(idx, d2, qptr, rptr, num_ref=pos_x.shape[0])
+    # offsets given by the caller may leave rows of x outside every cloud: their gradient is zero, filled by the backward
+    return _InterpolateRows.apply(x, qptr, rptr, idx, d2, tptr, tedge, tcoef, mq, mr, pos_y.shape[0], 0, ptr_x is None)

@@ -1,5 +1,6 @@
 """Propagation of per-point values from a sampled, device-resident dataset back to the points or vertices it was sampled from
-(csrc/interp.hip: ``dc_knn_cross`` once per dataset, ``dc_knn_interpolate`` per use) -- PointNet++-style feature propagation,
+(csrc/interp.hip: ``dc_knn_cross`` once per dataset, ``dc_knn_interpolate`` per use; with ``differentiable=True`` also
+``dc_knn_cross_transpose`` once and ``dc_knn_interpolate_backward`` per backward) -- PointNet++-style feature propagation,
 ``torch_geometric.nn.knn_interpolate`` for a whole store.
 
 What it closes: every stage of the device pipeline (``DeviceMeshDataset.sample_points``, ``DeviceDataset.geodesic_subsample``)
@@ -14,12 +15,16 @@ points of a shape, or on a mesh's vertices.
     prop = Propagator(test, meshes, k=3)                                 # target: a DeviceMeshDataset (its vertices)
     vertex_logits = prop.apply(logits, (0, len(test)))
 
-Inference only: no autograd, no backward kernel.  There is no CPU path.
+    prop = Propagator(train, full, k=3, differentiable=True)            # a loss on ALL points of a shape trains the network
+    loss = F.cross_entropy(prop.apply(logits, (c0, c1)), full.y_point[t0:t1])
+
+Inference only by default; ``differentiable=True`` adds the gradient w.r.t. the propagated VALUES (an ordered, atomics-free sum:
+bit-reproducible).  Positions are never differentiated.  There is no CPU path.
 """
 import numpy as np
 import torch
 
-from .geometry.interpolate import MAX_K, interpolate_rows, knn_cross
+from .geometry.interpolate import MAX_K, _InterpolateRows, interpolate_rows, knn_cross, knn_cross_transpose
 
 __all__ = ["Propagator", "target_view"]
 
@@ -50,9 +55,15 @@ class Propagator:
     8 k bytes per target row.  No synchronise: the sizes are the stores' host arrays.
 
     ``apply(values, clouds)`` interpolates source-resolution rows to target rows (``w = 1 / max(d^2, 1e-16)``, PyG's
-    ``knn_interpolate``); ``labels(pred)`` is the k = 1 label transfer, a gather.  Inference only: no autograd, no backward."""
+    ``knn_interpolate``); ``labels(pred)`` is the k = 1 label transfer, a gather.
 
-    def __init__(self, source, target, k=3, clouds_per_launch=4096):
+    ``differentiable=False`` (the default) is inference only: no autograd, no backward.  With ``True`` the constructor also builds
+    the store-wide transposed lists once (``knn_cross_transpose``: per valid slot an int64 edge id and an fp32 coefficient, i.e.
+    at most 12 k further bytes per target row, plus 8 bytes per source row of list offsets), and ``apply`` joins the autograd
+    graph when ``values`` requires grad and grad mode is on: the backward is one launch of an ordered sum over those lists, no
+    atomics, the same bits on every run.  There is no gradient for positions."""
+
+    def __init__(self, source, target, k=3, clouds_per_launch=4096, differentiable=False):
         k, per = int(k), int(clouds_per_launch)
         if not 1 <= k <= MAX_K:
             raise ValueError(f"Propagator: k = {k} outside [1, {MAX_K}]")
@@ -81,6 +92,9 @@ class Propagator:
                 if mq:
                     knn_cross(tpos, source.pos, k, ptr_query=tptr[lo:hi + 1], ptr_ref=self.sptr[lo:hi + 1], max_query_cloud=mq,
                               out=(self.idx, self.d2))
+            self.differentiable = bool(differentiable)
+            self.lists = knn_cross_transpose(self.idx, self.d2, tptr, self.sptr, num_ref=int(self.soff[-1])) \
+                if self.differentiable else None
         self._ranges = {}
 
     def __len__(self):
@@ -100,10 +114,11 @@ class Propagator:
                                           (int(self.soff[c0]), int(self.soff[c1])))
         return r
 
-    @torch.no_grad()
     def apply(self, values, clouds=None, out=None):
         """values: DEVICE fp32 ``[source rows of the clouds, C]`` (rows may be strided), the clouds ``(c0, c1)`` a contiguous range
-        of the set (default: all) -> fp32 ``[target rows of those clouds, C]``.  One launch; no synchronise."""
+        of the set (default: all) -> fp32 ``[target rows of those clouds, C]``.  One launch; no synchronise.  On a
+        ``differentiable`` propagator a ``values`` that requires grad (grad mode on) gives a result on the autograd graph -- the
+        same forward bits; ``out`` cannot be combined with that.  Otherwise nothing is recorded."""
         clouds = (0, len(self)) if clouds is None else clouds
         c0, c1 = int(clouds[0]), int(clouds[1])
         q, s, _, (t0, t1), (s0, s1) = self.cloud_range((c0, c1))
@@ -111,7 +126,17 @@ class Propagator:
             raise ValueError(f"Propagator.apply: values must hold the {s1 - s0} source rows of clouds {(c0, c1)}, got "
                              f"{tuple(values.shape)}")
         mq = int(self.tsizes[c0:c1].max()) if c1 > c0 else 0
-        return interpolate_rows(values, q, s, self.idx[t0:t1], self.d2[t0:t1], mq, n_query=t1 - t0, out=out)
+        if self.differentiable and values.requires_grad and torch.is_grad_enabled():
+            if out is not None:
+                raise ValueError("Propagator.apply: out= cannot receive a result that is recorded by autograd")
+            mr = int(self.ssizes[c0:c1].max()) if c1 > c0 else 0
+            tptr, tedge, tcoef = self.lists
+            # the store-wide lists name target rows of the STORE: the range's first row is subtracted (edge_base); every source
+            # row of the range lies in one of its clouds, so the backward writes the whole gradient
+            return _InterpolateRows.apply(values, q, s, self.idx[t0:t1], self.d2[t0:t1], tptr[s0:s1 + 1], tedge, tcoef, mq, mr,
+                                          t1 - t0, t0, True)
+        with torch.no_grad():
+            return interpolate_rows(values, q, s, self.idx[t0:t1], self.d2[t0:t1], mq, n_query=t1 - t0, out=out)
 
     @torch.no_grad()
     def labels(self, pred, clouds=None):

@@ -762,7 +762,8 @@ int dc_mesh_sample(const float* vert, const int32_t* face, const int64_t* vptr, 
 
 /* ---- propagation from a sampled cloud back to its source: two-set kNN and interpolation (csrc/interp.hip, csrc/interp_math.h) -- */
 /* Replaces torch_cluster.knn(x, y, k, batch_x, batch_y) as torch_geometric.nn.knn_interpolate calls it: for each of B cloud
- * pairs, the k nearest REFERENCE points of every QUERY point.  Inference only (no backward exists).
+ * pairs, the k nearest REFERENCE points of every QUERY point.  The result carries no gradient: positions and distances are not
+ * differentiated (dc_knn_interpolate_backward below is the gradient w.r.t. the interpolated features only).
  * Order (the contract of dc_knn): fp32 ((dx*dx+dy*dy)+dz*dz) without contraction, ascending, ties by lower reference index.
  *   query, ref  DEVICE [*,3] fp32 rows
  *   qptr, rptr  DEVICE [B+1] ABSOLUTE row offsets of the B clouds into query / ref (a slice of a store's offsets serves)
@@ -781,7 +782,8 @@ int dc_knn_cross(const float* query, const int64_t* qptr, const float* ref, cons
  * out[qptr[b] + i, c] = sum_s w_s x[rptr[b] + idx_s, c] / sum_s w_s with w_s = 1.0f / fmaxf(d2_s, 1e-16f) (PyG's clamp), fp32,
  * slots in order s = 0 .. k-1, every operation rounded on its own, one division per channel (csrc/interp_math.h).  A slot with
  * idx outside [0, size of the reference cloud) is skipped and indexes nothing; a query with exactly one valid slot gets that row
- * copied bit for bit (k = 1 is an exact gather), one with no valid slot a row of zeros.  Inference only (no backward exists).
+ * copied bit for bit (k = 1 is an exact gather), one with no valid slot a row of zeros.  Backward w.r.t. x:
+ * dc_knn_cross_transpose + dc_knn_interpolate_backward; none w.r.t. positions or distances.
  *   x           DEVICE [*,ldx] fp32 reference rows, C <= ldx; out DEVICE [*,ldo] fp32, C <= ldo
  *   qptr, rptr, max_query_cloud, k, idx, d2   as in dc_knn_cross (the same grid: chunks of 256 queries x cloud pairs)
  * 16-byte loads / stores where the base pointer and the leading dimension allow, scalar otherwise: any C >= 1, the same bits.
@@ -792,6 +794,49 @@ int dc_knn_cross(const float* query, const int64_t* qptr, const float* ref, cons
 int dc_knn_interpolate(const float* x, int64_t ldx, int32_t C, const int64_t* qptr, const int64_t* rptr, int32_t B,
                        int64_t max_query_cloud, int32_t k, const int32_t* idx, const float* d2, float* out, int64_t ldo,
                        void* stream);
+
+/* Replaces what autograd records for torch_geometric.nn.knn_interpolate's gather (y = x[idx]: an index_add_ with floating-point
+ * atomics in the backward): the TRANSPOSED lists of a dc_knn_cross result, built once per search.  For every reference row r of
+ * the call (ABSOLUTE, as x is indexed: rptr[b] + j), its in-edges: all (q, s) of ITS pair with a valid slot idx[q, s] == j
+ * (0 <= idx < size of the reference cloud), named e = q * k + s with q the ABSOLUTE query row (the row of idx / d2), in
+ * ASCENDING e, and the coefficient of each (csrc/interp_math.h: 1.0f for the only valid slot of a query, else w_s / den with the
+ * forward's den bits).
+ *   qptr, rptr  DEVICE [B+1] ABSOLUTE row offsets, as in dc_knn_cross; any B >= 0 (nothing is gridded over the pairs)
+ *   num_query   HOST: the rows of idx / d2 (>= qptr[B]); rows outside every pair have no edge.  num_ref  HOST: the rows of x
+ *               (>= rptr[B]); a slot that would land past it is dropped
+ *   tptr        DEVICE int64 [num_ref + 1], every entry written: the list of row r is [tptr[r], tptr[r+1]); tptr[num_ref] = the
+ *               number of valid slots of the call
+ *   tedge       DEVICE int64 [num_query * k] (the first tptr[num_ref] entries are written); tcoef fp32, the same positions
+ *   workspace   DEVICE, 8-byte aligned, dc_knn_cross_transpose_workspace_bytes(num_query, num_ref, k) bytes (0: sizes out of range)
+ * Count (integer atomics), scan, unordered fill (integer atomic cursors), then a ranking pass that sorts every list, one fill
+ * position per thread: the outputs are a function of the inputs only.  No floating-point atomics.  k outside 1 .. 16, a negative B or
+ * size, num_query * k above 2^39 - 256, a null pointer or a workspace that is null, misaligned or too small: DC_ERR_ARG with a
+ * message, checked before anything touches the device.  Six launches, stream-ordered, no allocation, no synchronisation,
+ * capturable. */
+size_t dc_knn_cross_transpose_workspace_bytes(int64_t num_query, int64_t num_ref, int32_t k);
+int dc_knn_cross_transpose(const int64_t* qptr, const int64_t* rptr, int32_t B, int64_t num_query, int64_t num_ref, int32_t k,
+                           const int32_t* idx, const float* d2, int64_t* tptr, int64_t* tedge, float* tcoef, void* workspace,
+                           size_t workspace_bytes, void* stream);
+/* Replaces the backward of torch_geometric.nn.knn_interpolate w.r.t. x (autograd's index_add_ of the weighted rows: floating-point
+ * atomics, no run-to-run guarantee) on the lists of dc_knn_cross_transpose: dx[r, c] = 0, then for every in-edge of r in ascending order
+ * dx = dx + tcoef * g[e / k - edge_base, c], product and sum each rounded on their own (csrc/interp_math.h).  Every reference row
+ * of every pair of the call is written (a row without in-edges gets zeros): no fill pass is needed.  No gradient w.r.t. positions
+ * or distances exists.
+ *   g           DEVICE [num_g_rows, ldg] fp32, the gradient of the interpolated rows, C <= ldg; an edge whose row
+ *               e / k - edge_base falls outside [0, num_g_rows) is skipped
+ *   rptr        DEVICE [B+1] ABSOLUTE row offsets of the reference clouds into dx AND tptr; max_ref_cloud HOST, >= the largest
+ *               reference cloud: it sizes the grid only (chunks of 256 / ceil(C / 4) reference rows x cloud pairs)
+ *   tptr, tedge, tcoef   from dc_knn_cross_transpose; num_edges HOST: the entries of tedge / tcoef (a list is cut to it)
+ *   edge_base   a row offset: a contiguous range of clouds runs against lists built once for a whole store by passing
+ *               g = the range's rows, edge_base = its first row, tptr + the range's first reference row and rptr relative to it
+ *   dx          DEVICE [*, ldx] fp32, C <= ldx
+ * 16-byte loads / stores where the base pointer and the leading dimension allow, scalar otherwise: any C >= 1, the same bits.
+ * k outside 1 .. 16, C outside 1 .. 2^20, ldg or ldx below C, B above 65 535, max_ref_cloud outside [0, 2^31), a negative size or a
+ * null pointer: DC_ERR_ARG with a message, checked before anything touches the device; B = 0 or max_ref_cloud = 0 returns DC_OK.
+ * One launch, stream-ordered, no allocation, no synchronisation, no atomics, capturable. */
+int dc_knn_interpolate_backward(const float* g, int64_t ldg, int64_t num_g_rows, int32_t C, const int64_t* rptr, int32_t B,
+                                int64_t max_ref_cloud, int32_t k, const int64_t* tptr, const int64_t* tedge, const float* tcoef,
+                                int64_t num_edges, int64_t edge_base, float* dx, int64_t ldx, void* stream);
 
 #ifdef __cplusplus
 }
