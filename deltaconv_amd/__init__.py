@@ -15,7 +15,7 @@ _os.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")
 
 from . import geometry, nn, models, transforms, datasets, optim, loader, evaluate, meshes, propagate, train   # noqa: F401
 from .data import Batch              # noqa: F401
-from .loader import DeviceDataset, DeviceLoader, RandomJitter   # noqa: F401
+from .loader import DeviceDataset, DeviceLoader, RandomJitter, random_split   # noqa: F401
 from .evaluate import GraphedEvalStep, DeviceEvaluator   # noqa: F401
 from .train import DeviceTrainer   # noqa: F401
 from .meshes import DeviceMeshDataset   # noqa: F401

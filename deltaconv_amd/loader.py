@@ -32,7 +32,7 @@ from ._lib import lib
 from .data import Batch
 from .geometry.graph import PtrInfo
 
-__all__ = ["DeviceDataset", "DeviceLoader", "RandomJitter", "translate_transforms",
+__all__ = ["DeviceDataset", "DeviceLoader", "RandomJitter", "translate_transforms", "translate_normalize", "random_split",
            "OP_SCALE", "OP_ROTATE", "OP_TRANSLATE", "OP_NORMAL_JITTER", "OP_POINT_JITTER", "MAX_OPS"]
 
 # op codes of csrc/batch_math.h
@@ -103,6 +103,63 @@ def translate_transforms(transform, has_norm=True):
     return ops
 
 
+def _sequence(transform):
+    if transform is None:
+        return []
+    if isinstance(transform, (list, tuple)):
+        return list(transform)
+    return list(transform.transforms) if hasattr(transform, "transforms") else [transform]
+
+
+def translate_normalize(transform, has_face=False):
+    """A transform | a ``Compose`` / list / tuple of them -> the op list ``[(code, p0, p1), ...]`` of csrc/shape_norm.hip, in order.
+    ``NormalizeScale(norm_ord 2 | inf, scaling_factor)``, ``NormalizeArea()`` (a mesh store only) and ``NormalizeAxes()`` (its
+    ``max_points`` is accepted and ignored, as the reference ignores it); anything else, an empty chain or more than 4 ops raises
+    ``ValueError``."""
+    from .geometry.shape_norm import MAX_NORM_OPS, OP_NORM_AREA, OP_NORM_AXES, OP_NORM_SCALE
+    ops = []
+    for t in _sequence(transform):
+        if type(t) is T.NormalizeScale:
+            if t.norm_ord not in (2, float("inf")) or isinstance(t.norm_ord, bool):
+                raise ValueError(f"normalize: NormalizeScale(norm_ord={t.norm_ord!r}): the device op takes 2 and inf")
+            factor = float("nan") if t.scaling_factor is None else float(t.scaling_factor)
+            if t.scaling_factor is not None and factor != factor:
+                raise ValueError("normalize: NormalizeScale(scaling_factor=nan)")
+            ops.append((OP_NORM_SCALE, float(t.norm_ord), factor))
+        elif type(t) is T.NormalizeArea:
+            if not has_face:
+                raise ValueError("normalize: NormalizeArea needs faces: it runs on a DeviceMeshDataset, not on a point store")
+            ops.append((OP_NORM_AREA, 0.0, 0.0))
+        elif type(t) is T.NormalizeAxes:
+            ops.append((OP_NORM_AXES, 0.0, 0.0))
+        else:
+            raise ValueError(f"normalize: no device form of transform {t!r} ({type(t).__name__}); it takes NormalizeScale, "
+                             "NormalizeArea and NormalizeAxes (there is no CPU fallback)")
+    if not 1 <= len(ops) <= MAX_NORM_OPS:
+        raise ValueError(f"normalize: 1 .. {MAX_NORM_OPS} normalisation ops, got {len(ops)}")
+    return ops
+
+
+def shape_rows(sizes, indices):
+    """Host int64 array of the store rows of the shapes ``indices`` (in that order), from the host sizes."""
+    sizes = np.asarray(sizes, dtype=np.int64)
+    start = np.concatenate([[0], np.cumsum(sizes)])[:-1]
+    idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+    if idx.size and (idx.min() < 0 or idx.max() >= sizes.shape[0]):
+        raise ValueError(f"subset: indices must lie in [0, {sizes.shape[0]})")
+    n = sizes[idx]
+    first = np.concatenate([[0], np.cumsum(n)])[:-1]
+    return (np.repeat(start[idx] - first, n) + np.arange(int(n.sum()), dtype=np.int64)).astype(np.int64), idx, n
+
+
+def random_split(store, lengths, seed):
+    """The seeded split of experiments/train_shapeseg.py:46-50 for a device store: subsets whose indices are those of
+    ``torch.utils.data.random_split(range(len(store)), lengths, generator=torch.Generator().manual_seed(seed))``, in its order
+    (``lengths``: counts, or fractions that sum to 1, as torch takes them).  Pure indexing: no kernel, any device."""
+    parts = torch.utils.data.random_split(range(len(store)), lengths, generator=torch.Generator().manual_seed(int(seed)))
+    return [store.subset(list(p.indices)) for p in parts]
+
+
 class DeviceDataset:
     """All clouds of a dataset concatenated on the device (the "store") + their sizes on the host."""
 
@@ -111,16 +168,18 @@ class DeviceDataset:
         self.ptr = ptr                                   # int64 [S+1], device
         self.sizes = np.asarray(sizes, dtype=np.int64)   # host
         self.device = pos.device
+        self.norm_stats = self.degenerate = None         # of the normalize pass that made this store
 
     def __len__(self):
         return int(self.sizes.shape[0])
 
     @classmethod
-    def from_dataset(cls, ds, device, fps=None, fps_seed=None):
+    def from_dataset(cls, ds, device, fps=None, fps_seed=None, normalize=None):
         """ds: a dataset with ``.items`` (ModelNet / ScanObjectNN / ShapeNet / ShapeSeg; its ``transform`` is not run) or any
         sequence of ``Data``.  Attributes taken: ``pos``, ``norm`` (or ``normal``), ``x``, ``y`` (one per cloud or one per
         point), ``category`` -- each either on every item or on none, as ``collate`` treats them.  ``fps``: reduce every cloud to
-        that many points with ``geodesic_subsample(fps, seed=fps_seed)`` once it is on the device (``None``: the clouds as they are)."""
+        that many points with ``geodesic_subsample(fps, seed=fps_seed)`` once it is on the device (``None``: the clouds as they are).
+        ``normalize``: NormalizeScale / NormalizeAxes transforms run on the device by ``normalize`` below, before ``fps``."""
         items = list(ds.items if hasattr(ds, "items") and not callable(ds.items) else ds)
         if not items:
             raise ValueError("DeviceDataset: empty dataset")
@@ -159,7 +218,46 @@ class DeviceDataset:
         up = lambda t: None if t is None else t.contiguous().to(device)
         f32 = lambda col: None if col is None else torch.cat(col).float()
         store = cls(up(f32(pos)), up(ptr), sizes, up(f32(norm)), up(f32(x)), up(y_point), up(y_cloud), up(category))
+        if normalize is not None:
+            store.normalize(normalize, out=store)
         return store if fps is None else store.geodesic_subsample(fps, seed=fps_seed)
+
+    def normalize(self, transforms, shapes_per_launch=4096, out=None):
+        """``T.NormalizeScale(norm_ord=, scaling_factor=)`` / ``T.NormalizeAxes()`` (one of them or a list / ``Compose`` of up to 4)
+        for every cloud of the store on the device: two launches per group of ``shapes_per_launch`` clouds (csrc/shape_norm.hip),
+        the same bits whatever the grouping.  -> a new store that shares every tensor with this one but ``pos`` (and ``norm``
+        where NormalizeAxes permuted its columns as it permutes the positions); ``out=store`` (this store, typically) is
+        normalised in place and returned.  The result carries ``norm_stats`` (device [S, n_ops, 8]: centre, scale, permutation per
+        op) and ``degenerate`` (host bool array: a centre or scale that is not finite or a scale <= 0) -- one synchronise at the
+        end of the pass.  ``NormalizeArea`` needs faces and raises ``ValueError`` here; so does any other transform."""
+        from .geometry.shape_norm import OP_NORM_AXES, normalize_store_rows
+        ops = translate_normalize(transforms, has_face=False)
+        res = out if out is not None else DeviceDataset(self.pos, self.ptr, self.sizes, self.norm, self.x, self.y_point, self.y_cloud,
+                                                        self.category)
+        if out is not None and (out.pos.shape != self.pos.shape or not np.array_equal(out.sizes, self.sizes)):
+            raise ValueError("normalize: `out` must be a store of the same clouds")
+        permutes = self.norm is not None and any(o[0] == OP_NORM_AXES for o in ops)
+        if permutes:
+            res.norm = self.norm.clone() if out is None else out.norm.copy_(self.norm)
+        res.pos, res.norm_stats, res.degenerate = normalize_store_rows(
+            self.pos, self.ptr, self.sizes, ops, shapes_per_launch, norm=res.norm if permutes else None,
+            out=None if out is None else out.pos)
+        return res
+
+    def subset(self, indices):
+        """A new store of the clouds ``indices`` (host sequence of dataset indices, kept in that order): rows, offsets, host sizes,
+        labels and categories follow.  Pure tensor indexing: no kernel, and it works on CPU tensors."""
+        rows, idx, n = shape_rows(self.sizes, indices)
+        dev = self.pos.device
+        rows_d, idx_d = torch.from_numpy(rows).to(dev), torch.from_numpy(idx).to(dev)
+        ptr = torch.zeros(idx.shape[0] + 1, dtype=torch.int64)
+        ptr[1:] = torch.from_numpy(np.cumsum(n))
+        take = lambda t, i: None if t is None else t[i].contiguous()
+        sub = DeviceDataset(take(self.pos, rows_d), ptr.to(dev), n, take(self.norm, rows_d), take(self.x, rows_d),
+                            take(self.y_point, rows_d), take(self.y_cloud, idx_d), take(self.category, idx_d))
+        sub.norm_stats = take(self.norm_stats, idx_d)
+        sub.degenerate = None if self.degenerate is None else np.asarray(self.degenerate)[idx]
+        return sub
 
     def geodesic_subsample(self, n_samples, start=None, seed=None, clouds_per_launch=1024):
         """A new store whose clouds each hold ``n_samples`` geodesic-farthest points of this one's: ``T.GeodesicFPS(n_samples)``

@@ -1,11 +1,12 @@
 """Device-resident triangle meshes and their surface sampling: all meshes of a dataset concatenated in HBM, ``num`` points
-drawn on every one of them in two launches per group of meshes (csrc/mesh.hip: ``dc_mesh_sample``).
+drawn on every one of them in two launches per group of meshes (csrc/mesh.hip: ``dc_mesh_sample``), after their normalisation
+in two more (csrc/shape_norm.hip: ``dc_shape_normalize``), with ``subset`` for the seeded splits of ``loader.random_split``.
 
 What it replaces: the ``SamplePoints`` step of the reference's data preparation (deltaconv/transforms/sample_points.py:22-59,
 called per shape from the ``pre_transform`` of experiments/train_modelnet.py:30-34, train_shrec.py:30-34 and
 train_shapeseg.py:28-34) -- a ``torch.multinomial`` over the faces and a handful of small ATen calls per shape.
 
-    meshes = DeviceMeshDataset.from_dataset(ModelNet(root, None, "40", True, pre_transform=T.NormalizeScale()), device)
+    meshes = DeviceMeshDataset.from_dataset(ModelNet(root, None, "40", True), device, normalize=T.NormalizeScale())
     store = meshes.sample_points(num_points * sampling_margin, seed=1).geodesic_subsample(num_points, seed=1)
     loader = DeviceLoader(store, 32, shuffle=True, drop_last=True, transform=aug, seed=1)
 
@@ -16,7 +17,7 @@ import numpy as np
 import torch
 
 from .geometry.mesh_sample import sample_points_batch
-from .loader import DeviceDataset
+from .loader import DeviceDataset, shape_rows, translate_normalize
 
 __all__ = ["DeviceMeshDataset", "sample_points_batch", "MESH_MAX_FACES"]
 
@@ -39,16 +40,19 @@ class DeviceMeshDataset:
         self.y_vert, self.y_cloud, self.category = y_vert, y_cloud, category
         self.device = vert.device
         self.total = self.degenerate = None                                       # of the last sample_points pass
+        self.norm_stats = None                                                    # of the normalize pass that made this store
 
     def __len__(self):
         return int(self.n_faces.shape[0])
 
     @classmethod
-    def from_dataset(cls, ds, device):
+    def from_dataset(cls, ds, device, normalize=None):
         """ds: a dataset with ``.items`` (ModelNet / ShapeSeg read with a ``pre_transform`` that keeps the faces; its
         ``transform`` is not run) or any sequence of items with ``pos [V,3]`` and ``face [3,F]`` as the OFF / PLY / OBJ readers
         give them.  Optional ``y`` (one per vertex or one per cloud) and ``category``, each on every item or on none.  Raises
-        ``ValueError`` unless every mesh has ``V >= 1``, ``1 <= F <= 2^24`` and every face id in ``[0, V)``."""
+        ``ValueError`` unless every mesh has ``V >= 1``, ``1 <= F <= 2^24`` and every face id in ``[0, V)``.  ``normalize``: NormalizeScale /
+        NormalizeArea / NormalizeAxes transforms run on the device by ``normalize`` below once the meshes are there, so the
+        dataset's ``pre_transform`` need not normalise on the host."""
         items = list(ds.items if hasattr(ds, "items") and not callable(ds.items) else ds)
         if not items:
             raise ValueError("DeviceMeshDataset: empty dataset")
@@ -88,8 +92,44 @@ class DeviceMeshDataset:
         cats = column("category")
         category = torch.stack([c.reshape(-1) for c in cats]).float() if cats is not None else None
         up = lambda t: None if t is None else t.contiguous().to(device)
-        return cls(up(torch.cat(verts)), up(torch.cat(faces)), up(torch.from_numpy(_offsets(n_verts))),
-                   up(torch.from_numpy(_offsets(n_faces))), n_verts, n_faces, up(y_vert), up(y_cloud), up(category))
+        store = cls(up(torch.cat(verts)), up(torch.cat(faces)), up(torch.from_numpy(_offsets(n_verts))),
+                    up(torch.from_numpy(_offsets(n_faces))), n_verts, n_faces, up(y_vert), up(y_cloud), up(category))
+        return store if normalize is None else store.normalize(normalize, out=store)
+
+    def normalize(self, transforms, shapes_per_launch=4096, out=None):
+        """``T.NormalizeScale(...)`` / ``T.NormalizeArea()`` / ``T.NormalizeAxes()`` (one of them or a list / ``Compose`` of up to 4,
+        e.g. the ``[T.NormalizeArea(), T.NormalizeAxes()]`` of experiments/train_shapeseg.py:28-30) for every mesh of the store on
+        the device: two launches per group of ``shapes_per_launch`` meshes (csrc/shape_norm.hip), the same bits whatever the
+        grouping.  NormalizeArea is the surface area over the face rows (``T.NormalizeArea`` on ``Data(pos, face=[F,3])``).
+        -> a new store that shares every tensor with this one but ``vert``; ``out=store`` (this store, typically) is normalised
+        in place and returned.  The result carries ``norm_stats`` (device [S, n_ops, 8]: centre, scale, permutation per op) and
+        ``degenerate`` (host bool array: a centre or scale that is not finite or a scale <= 0, e.g. a mesh without area under
+        NormalizeArea) -- one synchronise at the end of the pass.  Any other transform raises ``ValueError``."""
+        from .geometry.shape_norm import normalize_store_rows
+        ops = translate_normalize(transforms, has_face=True)
+        res = out if out is not None else DeviceMeshDataset(self.vert, self.face, self.vptr, self.fptr, self.n_verts, self.n_faces,
+                                                            self.y_vert, self.y_cloud, self.category)
+        if out is not None and (out.vert.shape != self.vert.shape or not np.array_equal(out.n_verts, self.n_verts)):
+            raise ValueError("normalize: `out` must be a store of the same meshes")
+        res.vert, res.norm_stats, res.degenerate = normalize_store_rows(
+            self.vert, self.vptr, self.n_verts, ops, shapes_per_launch, face=self.face, fptr=self.fptr,
+            out=None if out is None else out.vert)
+        return res
+
+    def subset(self, indices):
+        """A new store of the meshes ``indices`` (host sequence of dataset indices, kept in that order): vertex and face rows (face
+        ids are local to the mesh), offsets, host counts, labels and categories follow.  Pure tensor indexing: no kernel, and it
+        works on CPU tensors."""
+        vrows, idx, nv = shape_rows(self.n_verts, indices)
+        frows, _, nf = shape_rows(self.n_faces, indices)
+        dev = self.vert.device
+        up = lambda a: torch.from_numpy(a).to(dev)
+        vrows, frows, idx_d = up(vrows), up(frows), up(idx)
+        take = lambda t, i: None if t is None else t[i].contiguous()
+        sub = DeviceMeshDataset(take(self.vert, vrows), take(self.face, frows), up(_offsets(nv)), up(_offsets(nf)), nv, nf,
+                                take(self.y_vert, vrows), take(self.y_cloud, idx_d), take(self.category, idx_d))
+        sub.norm_stats = take(self.norm_stats, idx_d)
+        return sub
 
     def sample_points(self, num, include_normals=True, include_labels=False, seed=0, round=0, meshes_per_launch=4096):
         """``T.SamplePoints(num, include_normals=, include_labels=)`` for the whole store on the device -> a ``DeviceDataset`` whose

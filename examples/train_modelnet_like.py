@@ -5,7 +5,8 @@ the GPUs of one node.  No dataset ships with this repo (the reference downloads 
 the clouds are synthetic; with `--data <ModelNet40 root>` (raw/<category>/<train|test>/*.off) the reference's
 pipeline runs instead: NormalizeScale -> SamplePoints -> GeodesicFPS once, RandomScale + RandomTranslateGlobal
 per access (train_modelnet.py:29-49), through `deltaconv_amd.datasets`.  `--device-loader` keeps the prepared clouds on
-the GPU; `--device-fps` and `--device-sample` move GeodesicFPS, and SamplePoints with it, there as well; `--device-train` runs
+the GPU; `--device-fps` and `--device-sample` move GeodesicFPS, and SamplePoints with it, there as well, `--device-normalize`
+NormalizeScale too; `--device-train` runs
 the epochs themselves there (deltaconv_amd.DeviceTrainer: captured step, loss and accuracy read once per epoch).
 
     python examples/train_modelnet_like.py --epochs 3
@@ -92,6 +93,9 @@ def main(argv=None):
                     help="with --device-loader: SamplePoints and GeodesicFPS leave pre_transform (NormalizeScale alone stays); the "
                          "meshes go to the GPU and are sampled and reduced there, all shapes in a few launches "
                          "(DeviceMeshDataset.sample_points, then DeviceDataset.geodesic_subsample)")
+    ap.add_argument("--device-normalize", action="store_true",
+                    help="with --device-sample: NormalizeScale leaves pre_transform as well (nothing stays); the raw meshes go to the "
+                         "GPU and are normalised there, all shapes in two launches (DeviceMeshDataset.normalize)")
     ap.add_argument("--device-train", action="store_true",
                     help="with --device-loader: the training epoch on the device (deltaconv_amd.DeviceTrainer: the step replayed from "
                          "one captured graph, loss and accuracy kept on the device, one synchronise per epoch) instead of "
@@ -106,6 +110,8 @@ def main(argv=None):
         raise SystemExit("--resume continues from the state of a device trainer: it needs --device-train")
     if args.device_sample and not (args.data is not None and args.device_loader):
         raise SystemExit("--device-sample samples device-resident meshes: it needs --data and --device-loader")
+    if args.device_normalize and not args.device_sample:
+        raise SystemExit("--device-normalize normalises the device-resident meshes of --device-sample: it needs --device-sample")
     if args.device_fps and not (args.data is not None and args.device_loader):
         raise SystemExit("--device-fps samples a device-resident dataset: it needs --data and --device-loader")
     if args.device_eval and not (args.data is not None and args.device_loader):
@@ -130,7 +136,7 @@ def main(argv=None):
         pre = (T.NormalizeScale(), T.SamplePoints(args.num_points * args.sampling_margin, include_normals=True))
         pre = Compose(pre if args.device_fps else pre + (T.GeodesicFPS(args.num_points),))
         if args.device_sample:                                   # the meshes themselves are stored: faces stay
-            pre = T.NormalizeScale()
+            pre = None if args.device_normalize else T.NormalizeScale()
         aug = Compose((T.RandomScale((4 / 5, 5 / 4)), T.RandomTranslateGlobal(0.1)))
         tr = ModelNet(args.data, None, "40", True, transform=aug, pre_transform=pre)
         te = ModelNet(args.data, None, "40", False, pre_transform=pre)
@@ -138,7 +144,8 @@ def main(argv=None):
         # the same recipe, drawn and applied on the device; every rank takes its share of one permutation per epoch
         fps = args.num_points if args.device_fps else None      # same start points on every rank: one dataset, many shares
         if args.device_sample:                                  # same draws on every rank: seeds, not the global generator
-            store = lambda ds: deltaconv.DeviceMeshDataset.from_dataset(ds, dev).sample_points(
+            norm = T.NormalizeScale() if args.device_normalize else None
+            store = lambda ds: deltaconv.DeviceMeshDataset.from_dataset(ds, dev, normalize=norm).sample_points(
                 args.num_points * args.sampling_margin, seed=1).geodesic_subsample(args.num_points, seed=1)
         else:
             store = lambda ds: deltaconv.DeviceDataset.from_dataset(ds, dev, fps=fps, fps_seed=1)

@@ -760,6 +760,45 @@ int dc_mesh_sample(const float* vert, const int32_t* face, const int64_t* vptr, 
                    float* pos, float* norm, int64_t* y, int32_t* face_id, int64_t* total,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- per-shape normalisation of a store of clouds or meshes (csrc/shape_norm.hip, csrc/shape_norm_math.h) ------------------------ */
+/* Threads of the workgroup that reduces one shape: the fixed order of the fp64 sums depends on it (csrc/shape_norm_math.h), and the
+ * tests place their shape sizes around it. */
+int32_t dc_shape_normalize_threads(void);
+/* Replaces the per-shape host calls at the head of the reference's pre_transform -- deltaconv/transforms/normalize_scale.py:12-21
+ * (experiments/train_modelnet.py:30-34, train_shapenet.py:30-33), normalize_area.py:12-20 and normalize_axes.py:17-26
+ * (train_shapeseg.py:28-34): a chain of 1 to 4 ops applied to each of B shapes of a concatenated store.  Every op maps fp32 rows to
+ * fp32 rows and the next op sees the rounded result, as the host Compose does.
+ *   1 scale  (norm_ord, scaling_factor)  centre on the bounding-box middle, multiply by fl32(fl32(1 / ref) * 0.999999f); ref = the
+ *            largest row norm of the centred shape (norm_ord 2: fl32 of the fp64 square root; +inf: the largest |coordinate|), or
+ *            the scaling_factor where that is not NaN
+ *   2 area   (-, -)   centre, multiply by fl32(1 / sqrt(S / 2)), S the fp64 sum over the shape's face rows of the sampler's doubled
+ *            face area (csrc/mesh_math.h) in a fixed order that is a function of the shape alone; a face with an id outside
+ *            [0, V) counts 0.  This is the surface area over face ROWS, transforms.NormalizeArea on Data(pos, face=[F,3]);
+ *            normalize_area.py indexes data.face[:, 1], which on the [3,F] faces of its dataset reads the ids of face 1 -- in the
+ *            ShapeSeg recipe NormalizeAxes follows and rescales uniformly, so only the centring survives and the two agree
+ *   3 axes   (-, -)   columns in the stable order of ascending unbiased variance (fp64 sums of x and x*x in the same fixed order; a
+ *            tie or a NaN keeps the lower axis first, one row keeps the identity), multiply by fl32(1 / fl32(2 * max)) of the last
+ * The centre is fl32(fl32(max + min) / 2) per axis; all of it is csrc/shape_norm_math.h, which a numpy restatement reproduces bit
+ * for bit.  Non-finite arithmetic follows IEEE (a zero-area shape gets an infinite scale); nothing is clamped.
+ *   pos        DEVICE [N,3] fp32 rows of the store; ptr DEVICE [B+1] ABSOLUTE row offsets of the B shapes of this call (a slice of
+ *              the store's offsets); n_rows HOST = ptr[B] - ptr[0]: it sizes the grid only (rows past ptr[B] are not touched)
+ *   face, fptr DEVICE [Fs,3] vertex ids LOCAL to the shape and [B+1] ABSOLUTE offsets, the layout of dc_mesh_sample; NULL
+ *              unless the chain has an area op
+ *   op_codes   HOST [n_ops]; op_params HOST [n_ops,2]
+ *   pos_out    DEVICE [N,3], the same rows; may alias pos
+ *   norm       NULL, or DEVICE [N,3], in and out: an axes op permutes its columns as it permutes the positions (uniform scaling
+ *              leaves unit normals alone).  The reference has no normals at this point: an extension.  Not touched without an axes op
+ *   stats      NULL, or DEVICE [B,n_ops,8] fp32 per shape and op: centre 3, scale 1, permutation 3 (as floats), 0.  It is the
+ *              table the second launch reads; without it the table lives in workspace (DEVICE, 32 * B * n_ops bytes)
+ * An unknown op, n_ops outside 1 .. 4, B above 65 535, an area op without face / fptr, a norm_ord other than 2 or +inf: DC_ERR_ARG;
+ * neither stats nor a workspace that holds the table: DC_ERR_WORKSPACE; both with a message, checked before anything touches the
+ * device.  B = 0 returns DC_OK.  Two launches (one workgroup per shape builds the table, a grid over the rows of the call applies
+ * the chain), stream-ordered, capturable, no allocation, no synchronisation, no atomics: the outputs are a function of the
+ * inputs only. */
+int dc_shape_normalize(const float* pos, const int64_t* ptr, const int32_t* face, const int64_t* fptr, int32_t B, int64_t n_rows,
+                       const int32_t* op_codes, const float* op_params, int32_t n_ops, float* pos_out, float* norm, float* stats,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- propagation from a sampled cloud back to its source: two-set kNN and interpolation (csrc/interp.hip, csrc/interp_math.h) -- */
 /* Replaces torch_cluster.knn(x, y, k, batch_x, batch_y) as torch_geometric.nn.knn_interpolate calls it: for each of B cloud
  * pairs, the k nearest REFERENCE points of every QUERY point.  The result carries no gradient: positions and distances are not
