@@ -18,8 +18,8 @@
 //
 // The backward (csrc/interp_math.h: coef / pick / bwd4) is a transposed, ordered sum -- no floating-point atomics anywhere:
 //   transpose_*_kernel   the in-edge lists of every reference row, the shape of csc.hip: count (integer atomics, one thread per
-//                        slot), exclusive scan over ALL reference rows of the call (per-1024-row sums, then every block adds the
-//                        sums before it: the base of a pair is the valid slots of the earlier pairs), unordered fill (integer
+//                        slot), exclusive scan over ALL reference rows of the call (list_scan.h: per-1024-row sums, then every block adds
+//                        the sums before it: the base of a pair is the valid slots of the earlier pairs), unordered fill (integer
 //                        cursors), then the ranking: ONE FILL POSITION PER THREAD -- it finds its list through idx[e] and counts
 //                        the smaller entries of that list.  A list here can hold thousands of entries (a 200 k-vertex mesh
 //                        against 1024 samples: ~600 a row; a one-point cloud: every query), so the L^2 comparisons of a long list
@@ -31,6 +31,7 @@
 //                        Gather-bound, the cost of a thread is its list length.
 #include "common.h"
 #include "interp_math.h"
+#include "list_scan.h"
 
 namespace {
 
@@ -121,21 +122,6 @@ __global__ __launch_bounds__(IT_THREADS) void interpolate_kernel(const float* __
 }
 
 // ---- backward: transposed lists -----------------------------------------------------------------------------------------------
-typedef unsigned long long u64;
-constexpr int SC_THREADS = 1024;              // reference rows of a scan block
-
-__device__ __forceinline__ u64 block_sum(u64 v, u64* red) {          // red [SC_THREADS / 64]; every thread gets the sum
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    u64 s = 0;
-#pragma unroll
-    for (int w = 0; w < SC_THREADS / 64; ++w) s += red[w];
-    __syncthreads();
-    return s;
-}
-
 __global__ __launch_bounds__(IT_THREADS) void transpose_count_kernel(const int64_t* __restrict__ qptr,
                                                                      const int64_t* __restrict__ rptr, int B, int k,
                                                                      const int32_t* __restrict__ idx, long long ne,
@@ -144,41 +130,6 @@ __global__ __launch_bounds__(IT_THREADS) void transpose_count_kernel(const int64
     if (e >= ne) return;
     const long long r = dcinterp::pick(qptr, rptr, B, k, idx, e);
     if (r >= 0 && r < num_ref) atomicAdd(cnt + r, 1ull);
-}
-
-__global__ __launch_bounds__(SC_THREADS) void transpose_sum_kernel(const u64* __restrict__ cnt, long long num_ref,
-                                                                   u64* __restrict__ part) {
-    __shared__ u64 red[SC_THREADS / 64];
-    const long long r = (long long)blockIdx.x * SC_THREADS + threadIdx.x;
-    const u64 s = block_sum(r < num_ref ? cnt[r] : 0ull, red);
-    if (threadIdx.x == 0) part[blockIdx.x] = s;
-}
-
-// exclusive scan of cnt: tptr and the fill cursors (the cursors replace cnt)
-__global__ __launch_bounds__(SC_THREADS) void transpose_scan_kernel(u64* __restrict__ cnt, long long num_ref,
-                                                                    const u64* __restrict__ part, int64_t* __restrict__ tptr) {
-    __shared__ u64 red[SC_THREADS / 64];
-    __shared__ u64 sc[SC_THREADS];
-    const int tid = threadIdx.x;
-    u64 before = 0;
-    for (int i = tid; i < (int)blockIdx.x; i += SC_THREADS) before += part[i];
-    const u64 base = block_sum(before, red);
-    const long long r = (long long)blockIdx.x * SC_THREADS + tid;
-    const u64 c = r < num_ref ? cnt[r] : 0ull;
-    sc[tid] = c;
-    __syncthreads();
-    for (int off = 1; off < SC_THREADS; off <<= 1) {      // inclusive Hillis-Steele scan
-        const u64 v = tid >= off ? sc[tid - off] : 0ull;
-        __syncthreads();
-        sc[tid] += v;
-        __syncthreads();
-    }
-    if (r < num_ref) {
-        const u64 excl = base + sc[tid] - c;
-        tptr[r] = (int64_t)excl;
-        cnt[r] = excl;
-        if (r == num_ref - 1) tptr[num_ref] = (int64_t)(excl + c);
-    }
 }
 
 __global__ __launch_bounds__(IT_THREADS) void transpose_fill_kernel(const int64_t* __restrict__ qptr,
@@ -343,8 +294,8 @@ DC_EXPORT int dc_knn_cross_transpose(const int64_t* qptr, const int64_t* rptr, i
     dc_zero_words(cnt, 2 * (long)num_ref, s);
     hipLaunchKernelGGL(transpose_count_kernel, dim3(eblocks), dim3(IT_THREADS), 0, s, qptr, rptr, (int)B, (int)k, idx, ne,
                        (long long)num_ref, cnt);
-    hipLaunchKernelGGL(transpose_sum_kernel, dim3(sblocks), dim3(SC_THREADS), 0, s, cnt, (long long)num_ref, part);
-    hipLaunchKernelGGL(transpose_scan_kernel, dim3(sblocks), dim3(SC_THREADS), 0, s, cnt, (long long)num_ref, part, tptr);
+    hipLaunchKernelGGL(list_sum_kernel, dim3(sblocks), dim3(SC_THREADS), 0, s, cnt, (long long)num_ref, part);
+    hipLaunchKernelGGL(list_scan_kernel, dim3(sblocks), dim3(SC_THREADS), 0, s, cnt, (long long)num_ref, part, tptr);
     hipLaunchKernelGGL(transpose_fill_kernel, dim3(eblocks), dim3(IT_THREADS), 0, s, qptr, rptr, (int)B, (int)k, idx, ne,
                        (long long)num_ref, cnt, unordered);
     hipLaunchKernelGGL(transpose_rank_kernel, dim3(eblocks), dim3(IT_THREADS), 0, s, qptr, rptr, (int)B, (int)k, idx, d2, ne,

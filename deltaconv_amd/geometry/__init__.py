@@ -5,4 +5,5 @@ from .utils import batch_dot      # noqa: F401
 from .fps import geodesic_fps, geodesic_fps_batch    # noqa: F401
 from .mesh_sample import sample_points_batch         # noqa: F401
 from .shape_norm import normalize_shapes_batch       # noqa: F401
+from .mesh_normals import vertex_face_lists, vertex_normals_batch    # noqa: F401
 from .interpolate import interpolate_rows_backward, knn_cross, knn_cross_transpose, knn_interpolate  # noqa: F401

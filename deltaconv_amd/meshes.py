@@ -1,6 +1,7 @@
 """Device-resident triangle meshes and their surface sampling: all meshes of a dataset concatenated in HBM, ``num`` points
 drawn on every one of them in two launches per group of meshes (csrc/mesh.hip: ``dc_mesh_sample``), after their normalisation
-in two more (csrc/shape_norm.hip: ``dc_shape_normalize``), with ``subset`` for the seeded splits of ``loader.random_split``.
+in two more (csrc/shape_norm.hip: ``dc_shape_normalize``), with ``subset`` for the seeded splits of ``loader.random_split``; and
+the meshes' own vertices as clouds, with per-vertex normals (csrc/mesh_normal.hip: ``vertex_normals``, ``vertex_cloud``).
 
 What it replaces: the ``SamplePoints`` step of the reference's data preparation (deltaconv/transforms/sample_points.py:22-59,
 called per shape from the ``pre_transform`` of experiments/train_modelnet.py:30-34, train_shrec.py:30-34 and
@@ -16,6 +17,7 @@ meshes are grouped into launches, and another ``round`` gives a fresh sample of 
 import numpy as np
 import torch
 
+from .geometry.mesh_normals import vertex_face_lists, vertex_normals_batch, weighting_code
 from .geometry.mesh_sample import sample_points_batch
 from .loader import DeviceDataset, shape_rows, translate_normalize
 
@@ -41,6 +43,7 @@ class DeviceMeshDataset:
         self.device = vert.device
         self.total = self.degenerate = None                                       # of the last sample_points pass
         self.norm_stats = None                                                    # of the normalize pass that made this store
+        self.vertex_lists = None                                                  # (vf_ptr, vf_edge) once vertex_normals built them
 
     def __len__(self):
         return int(self.n_faces.shape[0])
@@ -167,4 +170,52 @@ class DeviceMeshDataset:
                               None if include_labels else self.y_cloud, self.category)
         self.total = store.total = total
         self.degenerate = store.degenerate = total.cpu().numpy() == 0             # the one synchronise of the pass
+        return store
+
+    def vertex_normals(self, weighting="uniform", zero_count=None):
+        """``GenerateMeshNormals()`` (torch_geometric's, train_shapeseg.py:31) for the whole store on the device -> float32 [Vs,3],
+        one unit normal per vertex row: per face ``c = (p1 - p0) x (p2 - p0)``, which gives ``c / max(|c|, 1e-12)``
+        (``weighting="uniform"``, PyG's) or ``c`` (``"area"``) to each of its corners, summed per vertex in a fixed order and
+        normalised (``geometry.vertex_normals_batch``; no floating-point atomics, the same bits on every run).  A vertex without
+        incident face, or whose contributions cancel exactly, gets the zero vector; ``zero_count`` (device int32 [S]) receives
+        their number per mesh.  The face winding decides the sign: inconsistent winding is not repaired.  A vertex's normal is a
+        function of its mesh alone; permuting the faces of a mesh may change the last bits.  The vertex-to-corner lists are built
+        once and kept on the store as ``vertex_lists`` (a normalisation in place keeps them: they hold no coordinates; ``subset``
+        and a ``normalize`` that makes a new store start without)."""
+        weighting_code(weighting)
+        if self.vertex_lists is None:
+            self.vertex_lists = vertex_face_lists(self.face, self.vptr, self.fptr, int(self.vert.shape[0]))
+        return vertex_normals_batch(self.vert, self.face, self.vptr, self.fptr, self.vertex_lists, weighting, zero_count=zero_count)
+
+    @staticmethod
+    def _refuse_zero_normals(counts):
+        bad = np.flatnonzero(np.asarray(counts) != 0)
+        if bad.size:
+            first = ", ".join(f"mesh {int(i)}: {int(counts[i])}" for i in bad[:5])
+            raise ValueError(f"vertex_cloud: {bad.size} of {len(counts)} meshes have vertices with a zero normal (no incident face, or "
+                             f"face normals that cancel) -- {first}{', ...' if bad.size > 5 else ''}; pass allow_zero_normals=True "
+                             "to keep them")
+
+    def vertex_cloud(self, include_normals=True, include_labels=True, weighting="uniform", allow_zero_normals=False):
+        """The meshes' own vertices as a ``DeviceDataset`` -- what the human-body segmentation benchmark is scored on: ``pos`` IS
+        ``vert`` (shared, not copied), ``ptr`` / ``sizes`` the vertex offsets and counts, ``norm`` the ``vertex_normals(weighting)``
+        with ``include_normals``, ``y_point`` the per-vertex labels with ``include_labels`` (otherwise ``y_cloud`` passes through);
+        ``category`` and ``norm_stats`` carry over.  The result runs through ``normalize``, ``geodesic_subsample``, ``DeviceLoader``
+        (variable-size clouds are assembled eagerly), ``DeviceEvaluator``, ``DeviceTrainer`` and, with this store as target,
+        ``Propagator``.  With ``include_normals`` the per-mesh counts of zero normals are read back -- the one synchronise of the
+        pass -- and kept on the result as ``zero_normals`` (host int array); any non-zero count raises ``ValueError`` naming the
+        first few meshes unless ``allow_zero_normals``."""
+        weighting_code(weighting)
+        if include_labels and self.y_vert is None:
+            raise ValueError("vertex_cloud: include_labels needs one label per vertex on every mesh")
+        norm = counts = None
+        if include_normals:
+            zero = torch.empty(len(self), dtype=torch.int32, device=self.device)
+            norm = self.vertex_normals(weighting, zero_count=zero)
+            counts = zero.cpu().numpy().astype(np.int64)                          # the one synchronise of the pass
+            if not allow_zero_normals:
+                self._refuse_zero_normals(counts)
+        store = DeviceDataset(self.vert, self.vptr, self.n_verts, norm, None, self.y_vert if include_labels else None,
+                              None if include_labels else self.y_cloud, self.category)
+        store.norm_stats, store.zero_normals = self.norm_stats, counts
         return store

@@ -14,7 +14,7 @@ import torch
 from ..geometry.fps import geodesic_fps
 
 __all__ = ["NormalizeScale", "NormalizeArea", "NormalizeAxes", "RandomScale", "RandomTranslateGlobal",
-           "RandomRotate", "RandomNormals", "SamplePoints", "GeodesicFPS"]
+           "RandomRotate", "RandomNormals", "SamplePoints", "GeodesicFPS", "GenerateMeshNormals"]
 
 
 class _Transform:
@@ -206,6 +206,32 @@ class SamplePoints(_Transform):
             data.y = data.y[face[0]]
         if self.remove_faces:
             data.face = None
+        return data
+
+
+class GenerateMeshNormals(_Transform):
+    """torch_geometric's ``GenerateMeshNormals`` (train_shapeseg.py:31), restated: per-vertex normals of a triangle mesh into
+    ``data.norm`` (``data.face`` is [3,F] here).  Per face ``c = (p1 - p0) x (p2 - p0)``; a face gives ``c / max(|c|, 1e-12)``
+    (``weighting="uniform"``, PyG's) or ``c`` itself (``"area"``) to each of its corners, a vertex gets ``s / max(|s|, 1e-12)`` of
+    the sum ``s`` over its incident corners: the zero vector without incident face.  The face winding decides the sign;
+    inconsistent winding is not repaired.  ``DeviceMeshDataset.vertex_normals`` is the device form, in a fixed summation order."""
+
+    def __init__(self, weighting="uniform"):
+        if weighting not in ("uniform", "area"):
+            raise ValueError(f"GenerateMeshNormals: weighting must be 'uniform' or 'area', got {weighting!r}")
+        self.weighting = weighting
+
+    def _args(self):
+        return "" if self.weighting == "uniform" else f"weighting={self.weighting!r}"
+
+    def __call__(self, data):
+        pos, face = data.pos, data.face
+        assert pos.size(1) == 3 and face.size(0) == 3
+        vec = torch.linalg.cross(pos[face[1]] - pos[face[0]], pos[face[2]] - pos[face[0]], dim=1)
+        if self.weighting == "uniform":
+            vec = torch.nn.functional.normalize(vec, p=2, dim=-1)
+        total = torch.zeros_like(pos).index_add_(0, torch.cat([face[0], face[1], face[2]]), vec.repeat(3, 1))
+        data.norm = torch.nn.functional.normalize(total, p=2, dim=-1)
         return data
 
 

@@ -7,14 +7,17 @@ device once and
     DeviceMeshDataset.from_dataset(...).normalize([NormalizeArea, NormalizeAxes])
         .sample_points(num_points * sampling_margin, include_labels=True).geodesic_subsample(num_points)
 
-replaces the per-shape ``pre_transform`` (train_shapeseg.py:28-34; GenerateMeshNormals is left out: SamplePoints overwrites the
-normals it computes), ``deltaconv_amd.random_split`` the split of :46-50, ``DeviceLoader`` the augmentation of :37-41,
+replaces the per-shape ``pre_transform`` (train_shapeseg.py:28-34; GenerateMeshNormals is left out there: SamplePoints overwrites
+the normals it computes).  ``--vertex-clouds`` trains on the meshes' own vertices instead of surface samples:
+``meshes.vertex_cloud().geodesic_subsample(num_points)``, the vertex normals being the device form of GenerateMeshNormals
+(train_shapeseg.py:31).  ``deltaconv_amd.random_split`` the split of :46-50, ``DeviceLoader`` the augmentation of :37-41,
 ``DeviceTrainer`` the epoch and ``DeviceEvaluator`` the two evaluations.  No per-shape host call is left.  The device
 ``NormalizeArea`` is the surface area over face rows; in front of ``NormalizeAxes`` only its centring survives, so the shapes
 are the reference's.
 
     python examples/train_shapeseg_like.py --epochs 2                          # synthetic labelled meshes
     python examples/train_shapeseg_like.py --data /data/ShapeSeg --epochs 50   # raw/ShapeSeg/<SET>/raw/{meshes,segs}
+    python examples/train_shapeseg_like.py --epochs 2 --vertex-clouds          # vertices + vertex normals, no surface sampling
 """
 import argparse
 import json
@@ -53,6 +56,8 @@ def prepare(items, dev, args):
     meshes = deltaconv.DeviceMeshDataset.from_dataset(items, dev).normalize([T.NormalizeArea(), T.NormalizeAxes()])
     if meshes.degenerate.any():
         raise SystemExit(f"{int(meshes.degenerate.sum())} meshes without surface area or extent: nothing to normalise them by")
+    if args.vertex_clouds:
+        return meshes.vertex_cloud().geodesic_subsample(args.num_points, seed=args.seed)
     return meshes.sample_points(args.num_points * args.sampling_margin, include_normals=True, include_labels=True,
                                 seed=args.seed).geodesic_subsample(args.num_points, seed=args.seed)
 
@@ -67,6 +72,8 @@ def main(argv=None):
     ap.add_argument("--grad_kernel", type=float, default=1)
     ap.add_argument("--grad_regularizer", type=float, default=0.001)
     ap.add_argument("--sampling_margin", type=int, default=8)
+    ap.add_argument("--vertex-clouds", action="store_true",
+                    help="train on the meshes' vertices and vertex normals instead of surface samples")
     ap.add_argument("--layers", type=int, default=8, help="convolution layers (train_shapeseg.py:71: 8)")
     ap.add_argument("--channels", type=int, default=128, help="channels of every layer (train_shapeseg.py:71: 128)")
     ap.add_argument("--seed", type=int, default=1, help="of the split, the surface samples, the FPS starts and the loader")

@@ -877,6 +877,52 @@ int dc_knn_interpolate_backward(const float* g, int64_t ldg, int64_t num_g_rows,
                                 int64_t max_ref_cloud, int32_t k, const int64_t* tptr, const int64_t* tedge, const float* tcoef,
                                 int64_t num_edges, int64_t edge_base, float* dx, int64_t ldx, void* stream);
 
+/* ---- per-vertex normals of a store of triangle meshes (csrc/mesh_normal.hip, csrc/mesh_normal_math.h) --------------------------- */
+/* First half of what replaces GenerateMeshNormals() in the reference's ShapeSeg pre_transform (experiments/train_shapeseg.py:31,
+ * torch_geometric's transform: an index_add_ of the face normals onto their corners): the vertex-to-incident-corner lists of a whole
+ * store, built once.  For every vertex row v of the call (ABSOLUTE, as vert is indexed: vptr[b] + id), its corner slots
+ * e = 3 * face_row + corner (face_row ABSOLUTE, the row of face) with face[face_row, corner] == id, in ASCENDING e.  A face row
+ * with any id outside [0, V) of its mesh has no corner in any list; a face that names a vertex twice is in its list twice.
+ *   face        DEVICE [num_faces,3] int32 vertex ids LOCAL to the mesh, one row per triangle (the layout of dc_mesh_sample)
+ *   vptr, fptr  DEVICE [B+1] ABSOLUTE row offsets of the B meshes into vert / face (a slice of the store's offsets serves); any
+ *               B >= 0 (nothing is gridded over the meshes)
+ *   num_verts   HOST: the rows of vert (>= vptr[B]); a row outside every mesh of the call gets an empty list.  num_faces HOST: the
+ *               rows of face (>= fptr[B]); a row outside every mesh of the call is in no list
+ *   vf_ptr      DEVICE int64 [num_verts + 1], every entry written: the list of row v is [vf_ptr[v], vf_ptr[v+1])
+ *   vf_edge     DEVICE int64 [3 * num_faces] (the first vf_ptr[num_verts] entries are written)
+ *   workspace   DEVICE, 8-byte aligned, dc_mesh_vertex_faces_workspace_bytes(num_verts, num_faces) bytes (0: sizes out of range)
+ * Count (integer atomics), scan, unordered fill (integer atomic cursors), then a ranking pass that sorts every list, one fill
+ * position per thread: the outputs are a function of the inputs only.  No floating-point atomics.  A negative B or size,
+ * num_verts or 3 * num_faces above 2^39 - 256, a null pointer or a workspace that is null, misaligned or too small: DC_ERR_ARG with
+ * a message, checked before anything touches the device.  Six launches, stream-ordered, no allocation, no synchronisation,
+ * capturable. */
+size_t dc_mesh_vertex_faces_workspace_bytes(int64_t num_verts, int64_t num_faces);
+int dc_mesh_vertex_faces(const int32_t* face, const int64_t* vptr, const int64_t* fptr, int32_t B, int64_t num_verts,
+                         int64_t num_faces, int64_t* vf_ptr, int64_t* vf_edge, void* workspace, size_t workspace_bytes,
+                         void* stream);
+/* Second half of what replaces GenerateMeshNormals() of experiments/train_shapeseg.py:31, on the lists of dc_mesh_vertex_faces: per
+ * face a = p1 - p0, b = p2 - p0, c = a x b; a face gives c / max(|c|, 1e-12) (weighting 0, "uniform": torch_geometric's) or c
+ * itself (weighting 1, "area") to each of its corners; normals[v] = s / max(|s|, 1e-12) with s the sum over the list of v, SEQUENTIAL
+ * in list order from +0.  fp32, every operation rounded on its own, |x| = sqrt((x*x + y*y) + z*z) (csrc/mesh_normal_math.h, which
+ * a numpy restatement reproduces bit for bit).  A vertex without incident corner or with s = 0 gets the zero vector; a zero-area
+ * face gives zero.  The face winding decides the sign: inconsistent winding is not repaired.  A vertex's normal is a function of its
+ * mesh alone -- not of B, of the mesh's place in the store or of the grouping into calls; permuting a mesh's faces may change the
+ * last bits.
+ *   vert        DEVICE [num_verts,3] fp32; face, vptr, fptr, num_verts, num_faces as in dc_mesh_vertex_faces
+ *   vf_ptr, vf_edge   from dc_mesh_vertex_faces on the same store (a list is cut to [0, 3 * num_faces); an entry that names a
+ *               face row outside the vertex's mesh is skipped)
+ *   weighting   0 uniform, 1 area
+ *   normals     DEVICE [num_verts,3] fp32; every row of a mesh of the call is written, no other
+ *   zero_count  NULL, or DEVICE int32 [B]: per mesh the vertices that got the zero vector (integer atomics on counters zeroed by
+ *               the call: order-free)
+ * One vertex per thread, the contributions of its faces recomputed from the vertex rows: a thread's cost is its list length (a hub
+ * vertex with thousands of faces is correct, not fast).  A negative B or size, a size above 2^39 - 256, an unknown weighting or a
+ * null pointer: DC_ERR_ARG with a message, checked before anything touches the device; B = 0 or num_verts = 0 returns DC_OK.  One
+ * launch (two with zero_count), stream-ordered, no allocation, no synchronisation, no floating-point atomics, capturable. */
+int dc_mesh_vertex_normals(const float* vert, const int32_t* face, const int64_t* vptr, const int64_t* fptr, int32_t B,
+                           int64_t num_verts, int64_t num_faces, const int64_t* vf_ptr, const int64_t* vf_edge, int32_t weighting,
+                           float* normals, int32_t* zero_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
