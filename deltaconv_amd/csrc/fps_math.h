@@ -64,4 +64,19 @@ DC_HD unsigned long long workspace_bytes(long long N) {
     return n * K * 8 + n * K * 4 + (n + 1) * 8 + n * 4 + 4 * 256;
 }
 
+// ---- the sampler for clouds above MAX_POINTS (fps_sample_global_kernel): D in global memory, the frontier bit sets in LDS ----
+constexpr int LARGE_MAX_POINTS = 262144;      // 2 bit sets of n / 8 bytes = 64 KiB of LDS at the cap (DC_FPS_LARGE_MAX_POINTS)
+
+// 32-bit words of one frontier bit set of a cloud of n points; vertex u is bit (u & 31) of word (u >> 5)
+DC_HD int bitset_words(int n) { return (n + 31) >> 5; }
+
+// bytes of dynamic LDS of the kernel for a launch whose largest cloud has n points: the two bit sets
+DC_HD unsigned long long large_lds_bytes(int n) { return 2ull * (unsigned long long)bitset_words(n) * 4; }
+
+// bytes of workspace dc_geodesic_fps_large needs for N points in all: the blocks above, then D [N] 64-bit patterns, 256-byte aligned
+DC_HD unsigned long long large_workspace_bytes(long long N) {
+    if (N < 0) N = 0;
+    return workspace_bytes(N) + (unsigned long long)N * 8 + 256;
+}
+
 }  // namespace dcfps

@@ -3,7 +3,8 @@ of deltaconv/cpp).  Same validation, same return value; the native part is the d
 restatement in deltaconv_amd/csrc_host/fps.cpp behind a C ABI (include/deltaconv_host.h).
 
 ``geodesic_fps_batch`` is the same sampler for a batch of clouds that already live on the device (csrc/fps.hip behind
-``dc_geodesic_fps_batch``): the same picks as ``geodesic_fps`` from the same start point, all clouds in two launches."""
+``dc_geodesic_fps_batch``): the same picks as ``geodesic_fps`` from the same start point, all clouds in two launches.  With
+``large=True`` clouds above that kernel's cap go through ``dc_geodesic_fps_large``, whose distance vector lives in global memory."""
 import ctypes
 import os
 import warnings
@@ -46,6 +47,8 @@ def geodesic_fps(points, n_samples, seed=None):
 
 
 FPS_MAX_POINTS = 16384        # DC_FPS_MAX_POINTS: a cloud's distance vector lives in the LDS of one workgroup (csrc/fps_math.h)
+FPS_LARGE_MAX_POINTS = 262144 # DC_FPS_LARGE_MAX_POINTS: the distance vector in global memory, two frontier bit sets in LDS
+FPS_LARGE_POINTS_PER_LAUNCH = 1 << 20   # points of a group of large clouds: its workspace holds 140 bytes per point (140 MiB)
 
 
 def fps_starts(sizes, seed=None, first=0):
@@ -64,8 +67,9 @@ def fps_starts(sizes, seed=None, first=0):
                      for i, n in enumerate(sizes)], dtype=np.int32).reshape(-1)
 
 
-def _fps_device(pos, ptr_host, n_samples, start_host):
-    """One launch pair over the clouds ptr_host (numpy int64 [B+1], ptr_host[0] = 0) of pos -> int32 [B, n_samples] on the device."""
+def _fps_device(pos, ptr_host, n_samples, start_host, large=False):
+    """One launch pair over the clouds ptr_host (numpy int64 [B+1], ptr_host[0] = 0) of pos -> int32 [B, n_samples] on the device.
+    ``large``: through ``dc_geodesic_fps_large`` (clouds of 1 .. FPS_LARGE_MAX_POINTS points) instead of the LDS kernel."""
     import torch
     from .._lib import lib
     b = int(ptr_host.shape[0]) - 1
@@ -74,29 +78,61 @@ def _fps_device(pos, ptr_host, n_samples, start_host):
         return out
     ptr_host = np.ascontiguousarray(ptr_host, dtype=np.int64)
     start_host = np.ascontiguousarray(start_host, dtype=np.int32)
-    need = int(lib.raw("dc_geodesic_fps_workspace_bytes")(int(ptr_host[-1])))
+    entry, sizer = (("dc_geodesic_fps_large", "dc_geodesic_fps_large_workspace_bytes") if large else
+                    ("dc_geodesic_fps_batch", "dc_geodesic_fps_workspace_bytes"))
+    need = int(lib.raw(sizer)(int(ptr_host[-1])))
     ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=pos.device)
     sizes = ptr_host[1:] - ptr_host[:-1]
-    lib.call("dc_geodesic_fps_batch", pos, 1 if pos.dtype == torch.float64 else 0, ctypes.c_void_p(ptr_host.ctypes.data), b,
+    lib.call(entry, pos, 1 if pos.dtype == torch.float64 else 0, ctypes.c_void_p(ptr_host.ctypes.data), b,
              int(sizes.max()), int(n_samples), ctypes.c_void_p(start_host.ctypes.data), out, ws, need)
     return out
 
 
-def _fps_launches(pos, ptr_host, n_samples, start_host, clouds_per_launch=1024):
-    """The clouds in groups of at most `clouds_per_launch` (the workspace holds 132 bytes per point of a group) -> int32 [B, n_samples]."""
+def _fps_launches(pos, ptr_host, n_samples, start_host, clouds_per_launch=1024, large=False):
+    """The clouds in groups of at most `clouds_per_launch` (the workspace holds 132 bytes per point of a group) -> int32 [B, n_samples].
+    ``large``: groups of at most FPS_LARGE_POINTS_PER_LAUNCH points as well (one cloud at least; 140 bytes per point)."""
     import torch
     b = int(ptr_host.shape[0]) - 1
-    if b <= clouds_per_launch:
-        return _fps_device(pos, ptr_host, n_samples, start_host)
-    parts = []
-    for lo in range(0, b, clouds_per_launch):
-        hi = min(b, lo + clouds_per_launch)
-        parts.append(_fps_device(pos[int(ptr_host[lo]):int(ptr_host[hi])], ptr_host[lo:hi + 1] - ptr_host[lo], n_samples,
-                                 start_host[lo:hi]))
-    return torch.cat(parts)
+    if not large:
+        if b <= clouds_per_launch:
+            return _fps_device(pos, ptr_host, n_samples, start_host)
+        bounds = list(range(0, b, clouds_per_launch)) + [b]
+    else:
+        bounds = [0]
+        for i in range(b):                               # cloud i opens a group where the open one is full by count or by points
+            lo = bounds[-1]
+            if i > lo and (i - lo >= clouds_per_launch or ptr_host[i + 1] - ptr_host[lo] > FPS_LARGE_POINTS_PER_LAUNCH):
+                bounds.append(i)
+        bounds.append(b)
+    parts = [_fps_device(pos[int(ptr_host[lo]):int(ptr_host[hi])], ptr_host[lo:hi + 1] - ptr_host[lo], n_samples, start_host[lo:hi],
+                         large) for lo, hi in zip(bounds[:-1], bounds[1:])]
+    return parts[0] if len(parts) == 1 else torch.cat(parts)
 
 
-def geodesic_fps_batch(pos, ptr, n_samples, start=None, seed=None):
+def _fps_by_size_class(pos, ptr_host, n_samples, start_host, clouds_per_launch=1024):
+    """Every cloud on the device, whatever its size up to FPS_LARGE_MAX_POINTS: clouds of at most FPS_MAX_POINTS points through
+    the LDS kernel, the others through the global-memory kernel; rows in input order -> int64 [B, n_samples].  Both kernels give
+    a cloud the same picks, so the result does not depend on which side of the cap a cloud falls."""
+    import torch
+    sizes = ptr_host[1:] - ptr_host[:-1]
+    big = sizes > FPS_MAX_POINTS
+    if not big.any():
+        return _fps_launches(pos, ptr_host, n_samples, start_host, clouds_per_launch).long()
+    if big.all():
+        return _fps_launches(pos, ptr_host, n_samples, start_host, clouds_per_launch, large=True).long()
+    dev = pos.device
+    ids = torch.empty((sizes.size, int(n_samples)), dtype=torch.int64, device=dev)
+    for mask, is_large in ((~big, False), (big, True)):
+        sel = np.flatnonzero(mask)
+        rows = torch.from_numpy(np.concatenate([np.arange(ptr_host[i], ptr_host[i + 1]) for i in sel])).to(dev)
+        ptr_sel = np.zeros(sel.size + 1, dtype=np.int64)
+        ptr_sel[1:] = np.cumsum(sizes[sel])
+        ids[torch.from_numpy(sel).to(dev)] = _fps_launches(pos[rows], ptr_sel, n_samples, start_host[sel], clouds_per_launch,
+                                                           large=is_large).long()
+    return ids
+
+
+def geodesic_fps_batch(pos, ptr, n_samples, start=None, seed=None, large=False):
     """Geodesic farthest-point sampling of every cloud of a batch on the device (reference: transforms/geodesic_fps.py:14-43
     over cpp/sampling.cpp:5-81, one host call per shape).
 
@@ -104,7 +140,10 @@ def geodesic_fps_batch(pos, ptr, n_samples, start=None, seed=None):
     ptr[B] = N.  -> DEVICE int64 [B, n_samples], ids local to the cloud: row b is what ``geodesic_fps(pos[ptr[b]:ptr[b+1]],
     n_samples)`` returns when it starts from the same point.  ``start``: the first sample of every cloud (B ids local to the
     cloud); otherwise ``fps_starts(sizes, seed)``.  Clouds of more than ``FPS_MAX_POINTS`` = 16 384 points, empty clouds, a
-    start outside its cloud and host tensors raise ``ValueError``; there is no CPU path (``geodesic_fps`` is the host sampler)."""
+    start outside its cloud and host tensors raise ``ValueError``; there is no CPU path (``geodesic_fps`` is the host sampler).
+    ``large=True``: clouds above ``FPS_MAX_POINTS`` are sampled too, by the kernel that keeps the distance vector in global
+    memory (``dc_geodesic_fps_large``, up to ``FPS_LARGE_MAX_POINTS`` = 262 144 points; above that ``ValueError``); the others
+    still go to the LDS kernel, and the rows come back in input order."""
     import torch
     if not torch.is_tensor(pos) or not pos.is_cuda:
         raise ValueError("geodesic_fps_batch: `pos` must be a tensor on a HIP device (geodesic_fps samples host arrays)")
@@ -118,7 +157,10 @@ def geodesic_fps_batch(pos, ptr, n_samples, start=None, seed=None):
     sizes = ptr_host[1:] - ptr_host[:-1]
     if sizes.size and sizes.min() < 1:
         raise ValueError("geodesic_fps_batch: empty cloud")
-    if sizes.size and sizes.max() > FPS_MAX_POINTS:
+    if large and sizes.size and sizes.max() > FPS_LARGE_MAX_POINTS:
+        raise ValueError(f"geodesic_fps_batch: a cloud of {int(sizes.max())} points; the device sampler for large clouds takes "
+                         f"at most {FPS_LARGE_MAX_POINTS} per cloud (use geodesic_fps on the host for larger ones)")
+    if not large and sizes.size and sizes.max() > FPS_MAX_POINTS:
         raise ValueError(f"geodesic_fps_batch: a cloud of {int(sizes.max())} points; the device sampler takes at most "
                          f"{FPS_MAX_POINTS} per cloud (use geodesic_fps on the host for larger ones)")
     if start is None:
@@ -127,4 +169,6 @@ def geodesic_fps_batch(pos, ptr, n_samples, start=None, seed=None):
         start_host = (start.detach().cpu().numpy() if torch.is_tensor(start) else np.asarray(start)).astype(np.int64).reshape(-1)
         if start_host.shape != sizes.shape or (start_host < 0).any() or (start_host >= sizes).any():
             raise ValueError("geodesic_fps_batch: `start` must hold one point of every cloud (ids local to the cloud)")
+    if large:
+        return _fps_by_size_class(pos.contiguous(), ptr_host, n_samples, start_host)
     return _fps_launches(pos.contiguous(), ptr_host, n_samples, start_host).long()

@@ -174,11 +174,12 @@ class DeviceDataset:
         return int(self.sizes.shape[0])
 
     @classmethod
-    def from_dataset(cls, ds, device, fps=None, fps_seed=None, normalize=None):
+    def from_dataset(cls, ds, device, fps=None, fps_seed=None, normalize=None, fps_large="host"):
         """ds: a dataset with ``.items`` (ModelNet / ScanObjectNN / ShapeNet / ShapeSeg; its ``transform`` is not run) or any
         sequence of ``Data``.  Attributes taken: ``pos``, ``norm`` (or ``normal``), ``x``, ``y`` (one per cloud or one per
         point), ``category`` -- each either on every item or on none, as ``collate`` treats them.  ``fps``: reduce every cloud to
-        that many points with ``geodesic_subsample(fps, seed=fps_seed)`` once it is on the device (``None``: the clouds as they are).
+        that many points with ``geodesic_subsample(fps, seed=fps_seed, large=fps_large)`` once it is on the device (``None``: the
+        clouds as they are).
         ``normalize``: NormalizeScale / NormalizeAxes transforms run on the device by ``normalize`` below, before ``fps``."""
         items = list(ds.items if hasattr(ds, "items") and not callable(ds.items) else ds)
         if not items:
@@ -220,7 +221,7 @@ class DeviceDataset:
         store = cls(up(f32(pos)), up(ptr), sizes, up(f32(norm)), up(f32(x)), up(y_point), up(y_cloud), up(category))
         if normalize is not None:
             store.normalize(normalize, out=store)
-        return store if fps is None else store.geodesic_subsample(fps, seed=fps_seed)
+        return store if fps is None else store.geodesic_subsample(fps, seed=fps_seed, large=fps_large)
 
     def normalize(self, transforms, shapes_per_launch=4096, out=None):
         """``T.NormalizeScale(norm_ord=, scaling_factor=)`` / ``T.NormalizeAxes()`` (one of them or a list / ``Compose`` of up to 4)
@@ -259,7 +260,7 @@ class DeviceDataset:
         sub.degenerate = None if self.degenerate is None else np.asarray(self.degenerate)[idx]
         return sub
 
-    def geodesic_subsample(self, n_samples, start=None, seed=None, clouds_per_launch=1024):
+    def geodesic_subsample(self, n_samples, start=None, seed=None, clouds_per_launch=1024, large="host"):
         """A new store whose clouds each hold ``n_samples`` geodesic-farthest points of this one's: ``T.GeodesicFPS(n_samples)``
         (reference: transforms/geodesic_fps.py:14-43) for the whole dataset on the device -- ``geometry.geodesic_fps_batch`` over
         groups of ``clouds_per_launch`` clouds, then ``pos``, ``norm``, ``x`` and per-point ``y`` gathered by the sample ids.  A
@@ -267,11 +268,22 @@ class DeviceDataset:
         ``start``: the first sample of every cloud (host sequence of ids local to the cloud); otherwise drawn per cloud from
         ``(seed, dataset index)`` (``geometry.fps.fps_starts``; ``seed=None``: at random), whatever ``clouds_per_launch`` is.
         A cloud above the device sampler's cap of 16 384 points goes through the host library (``geometry.geodesic_fps``, which
-        derives its start from a seed: an explicit ``start`` for such a cloud raises ``ValueError``) and its ids are uploaded."""
-        from .geometry.fps import FPS_MAX_POINTS, _fps_launches, fps_starts, geodesic_fps
+        derives its start from a seed: an explicit ``start`` for such a cloud raises ``ValueError``) and its ids are uploaded.
+        ``large="device"``: such a cloud is sampled on the device as well (``dc_geodesic_fps_large``, up to 262 144 points; above
+        that, or for a store on the CPU, ``ValueError``), from the same ``start`` / ``fps_starts`` point as any other cloud --
+        the picks do not depend on which side of the cap a cloud falls, nor on ``clouds_per_launch``."""
+        from .geometry.fps import (FPS_LARGE_MAX_POINTS, FPS_MAX_POINTS, _fps_by_size_class, _fps_launches, fps_starts,
+                                   geodesic_fps)
         m, s, dev = int(n_samples), len(self), self.device
         if m < 1 or int(clouds_per_launch) < 1:
             raise ValueError("geodesic_subsample: n_samples >= 1 and clouds_per_launch >= 1")
+        if large not in ("host", "device"):
+            raise ValueError(f"geodesic_subsample: large must be 'host' or 'device', got {large!r}")
+        if large == "device" and not self.pos.is_cuda:
+            raise ValueError("geodesic_subsample: large='device' needs a store on a HIP device")
+        if large == "device" and s and self.sizes.max() > FPS_LARGE_MAX_POINTS:
+            raise ValueError(f"geodesic_subsample: a cloud of {int(self.sizes.max())} points; the device sampler for large clouds "
+                             f"takes at most {FPS_LARGE_MAX_POINTS} per cloud")
         sizes = self.sizes
         if start is None:
             starts = fps_starts(sizes, seed)
@@ -285,6 +297,8 @@ class DeviceDataset:
         ids = torch.empty((s, m), dtype=torch.int64, device=dev)
         if small.size == s:
             ids = _fps_launches(self.pos, ptr_host, m, starts, int(clouds_per_launch)).long()
+        elif large == "device":
+            ids = _fps_by_size_class(self.pos, ptr_host, m, starts, int(clouds_per_launch))
         else:
             if start is not None:
                 raise ValueError(f"geodesic_subsample: a cloud above {FPS_MAX_POINTS} points is sampled by the host library, which "

@@ -89,6 +89,10 @@ def main(argv=None):
     ap.add_argument("--device-fps", action="store_true",
                     help="with --device-loader: GeodesicFPS leaves pre_transform; the oversampled clouds are reduced to num_points on "
                          "the device, all shapes in a few launches (DeviceDataset.geodesic_subsample) instead of one host call per shape")
+    ap.add_argument("--device-fps-large", action="store_true",
+                    help="with --device-fps or --device-sample: clouds of more than 16 384 points (num_points * sampling_margin above that) are reduced "
+                         "on the device too (geodesic_subsample(large='device'), up to 262 144 points) instead of through the host "
+                         "library")
     ap.add_argument("--device-sample", action="store_true",
                     help="with --device-loader: SamplePoints and GeodesicFPS leave pre_transform (NormalizeScale alone stays); the "
                          "meshes go to the GPU and are sampled and reduced there, all shapes in a few launches "
@@ -114,6 +118,8 @@ def main(argv=None):
         raise SystemExit("--device-normalize normalises the device-resident meshes of --device-sample: it needs --device-sample")
     if args.device_fps and not (args.data is not None and args.device_loader):
         raise SystemExit("--device-fps samples a device-resident dataset: it needs --data and --device-loader")
+    if args.device_fps_large and not (args.device_fps or args.device_sample):
+        raise SystemExit("--device-fps-large moves the large clouds of --device-fps / --device-sample to the device: it needs one of them")
     if args.device_eval and not (args.data is not None and args.device_loader):
         raise SystemExit("--device-eval evaluates from a device-resident test set: it needs --data and --device-loader")
 
@@ -143,12 +149,13 @@ def main(argv=None):
     if args.data is not None and args.device_loader:
         # the same recipe, drawn and applied on the device; every rank takes its share of one permutation per epoch
         fps = args.num_points if args.device_fps else None      # same start points on every rank: one dataset, many shares
+        fps_large = "device" if args.device_fps_large else "host"
         if args.device_sample:                                  # same draws on every rank: seeds, not the global generator
             norm = T.NormalizeScale() if args.device_normalize else None
             store = lambda ds: deltaconv.DeviceMeshDataset.from_dataset(ds, dev, normalize=norm).sample_points(
-                args.num_points * args.sampling_margin, seed=1).geodesic_subsample(args.num_points, seed=1)
+                args.num_points * args.sampling_margin, seed=1).geodesic_subsample(args.num_points, seed=1, large=fps_large)
         else:
-            store = lambda ds: deltaconv.DeviceDataset.from_dataset(ds, dev, fps=fps, fps_seed=1)
+            store = lambda ds: deltaconv.DeviceDataset.from_dataset(ds, dev, fps=fps, fps_seed=1, fps_large=fps_large)
         train = deltaconv.DeviceLoader(store(tr), args.batch_size, shuffle=True, drop_last=True, transform=aug, seed=1, rank=rank,
                                        world=world)
         test = deltaconv.DeviceLoader(store(te), args.batch_size)

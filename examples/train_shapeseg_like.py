@@ -57,7 +57,8 @@ def prepare(items, dev, args):
     if meshes.degenerate.any():
         raise SystemExit(f"{int(meshes.degenerate.sum())} meshes without surface area or extent: nothing to normalise them by")
     if args.vertex_clouds:
-        return meshes.vertex_cloud().geodesic_subsample(args.num_points, seed=args.seed)
+        return meshes.vertex_cloud().geodesic_subsample(args.num_points, seed=args.seed,
+                                                        large="device" if args.device_fps_large else "host")
     return meshes.sample_points(args.num_points * args.sampling_margin, include_normals=True, include_labels=True,
                                 seed=args.seed).geodesic_subsample(args.num_points, seed=args.seed)
 
@@ -74,6 +75,9 @@ def main(argv=None):
     ap.add_argument("--sampling_margin", type=int, default=8)
     ap.add_argument("--vertex-clouds", action="store_true",
                     help="train on the meshes' vertices and vertex normals instead of surface samples")
+    ap.add_argument("--device-fps-large", action="store_true",
+                    help="with --vertex-clouds: meshes of more than 16 384 vertices are reduced on the device too "
+                         "(geodesic_subsample(large='device'), up to 262 144 vertices) instead of through the host library")
     ap.add_argument("--layers", type=int, default=8, help="convolution layers (train_shapeseg.py:71: 8)")
     ap.add_argument("--channels", type=int, default=128, help="channels of every layer (train_shapeseg.py:71: 128)")
     ap.add_argument("--seed", type=int, default=1, help="of the split, the surface samples, the FPS starts and the loader")
@@ -84,6 +88,8 @@ def main(argv=None):
     ap.add_argument("--mesh_faces", type=int, default=4000, help="faces of a synthetic mesh")
     ap.add_argument("--resume", default=None, help="continue from the state a run of this script wrote (last_trainer.pt)")
     args = ap.parse_args(argv)
+    if args.device_fps_large and not args.vertex_clouds:
+        raise SystemExit("--device-fps-large samples the vertex clouds of --vertex-clouds: it needs --vertex-clouds")
 
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)

@@ -32,6 +32,7 @@ extern "C" {
 #define DC_ERR_LAUNCH (-2)
 #define DC_ERR_WORKSPACE (-3)
 #define DC_FPS_MAX_POINTS (16384) /* points per cloud dc_geodesic_fps_batch takes: 8 bytes of LDS per point in one workgroup */
+#define DC_FPS_LARGE_MAX_POINTS (262144) /* points per cloud dc_geodesic_fps_large takes: two bit sets of n / 8 bytes of LDS */
 
 int32_t dc_version(void);
 const char* dc_last_error(void);
@@ -722,6 +723,25 @@ size_t dc_geodesic_fps_workspace_bytes(int64_t N);
  * (checked before anything touches the device); B = 0 returns DC_OK.  ptr and start are copied in stream order and may be freed on
  * return.  No global atomics, no floating-point atomics: the output is a function of the inputs only.  Stream-ordered. */
 int dc_geodesic_fps_batch(const void* pos, int32_t pos_is_f64, const int64_t* ptr, int32_t B, int32_t max_cloud_size,
+                          int32_t n_samples, const int32_t* start, int32_t* out, void* workspace, size_t workspace_bytes,
+                          void* stream);
+/* Bytes of workspace dc_geodesic_fps_large needs for clouds of N points in all: dc_geodesic_fps_workspace_bytes(N) plus the
+ * distance vectors, 8 N bytes, 256-byte aligned (140 bytes per point).  Reference: deltaconv/cpp/sampling.cpp:30-31 (the
+ * distance vector the rounds of :42-50 keep lowering). */
+size_t dc_geodesic_fps_large_workspace_bytes(int64_t N);
+/* dc_geodesic_fps_batch for clouds above its cap -- the same per-shape host call of the reference's data preparation,
+ * deltaconv/transforms/geodesic_fps.py:14-43 over deltaconv/cpp/sampling.cpp:5-81, which has no size limit: the same graph
+ * launch, then a sampling kernel (one workgroup of 1 024 threads per cloud, every round inside the launch) that keeps the
+ * distance vector in the workspace and only the two frontier bit sets in LDS.  Relaxations meet in unsigned 64-bit integer
+ * minima at agent scope, and every later access to a distance is an agent-scope atomic load or store; a minimum does not depend
+ * on the order of its operands, so the picks are still a function of the inputs only, and for a cloud both entries take they
+ * are the same picks.  Arguments, checks and return codes as dc_geodesic_fps_batch, with
+ *   ptr        every cloud of 1 .. 262 144 points (DC_FPS_LARGE_MAX_POINTS); any size from 1 up is taken, not only sizes
+ *              above DC_FPS_MAX_POINTS
+ *   max_cloud_size  >= the largest cloud, <= 262 144
+ *   workspace  DEVICE, 8-byte aligned, >= dc_geodesic_fps_large_workspace_bytes(ptr[B]) bytes (else DC_ERR_WORKSPACE)
+ * No floating-point atomics.  Stream-ordered. */
+int dc_geodesic_fps_large(const void* pos, int32_t pos_is_f64, const int64_t* ptr, int32_t B, int32_t max_cloud_size,
                           int32_t n_samples, const int32_t* start, int32_t* out, void* workspace, size_t workspace_bytes,
                           void* stream);
 
