@@ -7,6 +7,7 @@ import sys
 import deltaconv_amd as _impl
 
 for _name in ("geometry", "geometry.grad_div_mls", "geometry.operators", "geometry.utils", "geometry.fps", "geometry.interpolate",
+              "geometry.connection",
               "nn", "nn.deltaconv", "nn.mlp", "nn.nonlin", "models", "models.deltanet_base",
               "models.deltanet_classification", "models.deltanet_segmentation", "transforms"):
     sys.modules[f"{__name__}.{_name}"] = importlib.import_module(f"deltaconv_amd.{_name}")

@@ -300,6 +300,35 @@ int dc_knn_sum(const int32_t* nbr, int32_t n, int32_t k, const float* h, int32_t
 int dc_knn_sum_backward(const int32_t* tptr, const int32_t* tedge, int32_t n, int32_t k, const float* dout, int32_t C,
                         int64_t ldo, float scale, float* dh, int64_t ldh, int32_t accumulate, void* stream);
 
+/* ---- parallel transport between tangent frames ------------------------------------------------
+ * build_transport                                       deltaconv/geometry/connection.py:6-47
+ * out[m] = (r00, r01, r10, r11), the 2 x 2 matrix (row-major) that takes a vector's coordinates in the source frame
+ * (sn, sx, sn x sx) to the target frame (tn, tx, ty); all arrays fp32 rows of 3, out [M,4].  nbr == NULL: the pair form
+ * (row m of all five arrays, the reference's call shape; k is ignored).  nbr given (int32 [N,k], M = N * k): the graph
+ * form, target = row m / k, source = row nbr[m]; sn / sx may be tn / tx.  One launch, one thread and one 16-byte store
+ * (out 16-byte aligned, else four dword stores) per edge, no [E,3] expansion.  The reference's cos / sin of atan2 are
+ * taken as x / r, y / r (csrc/connection_math.h), so the result has one fp32 value on every build. */
+int dc_build_transport(const float* tn, const float* tx, const float* ty, const float* sn, const float* sx,
+                       const int32_t* nbr, int32_t k, int64_t M, int32_t non_oriented, float* out, void* stream);
+/* angle_in_plane                                        deltaconv/geometry/connection.py:50-59
+ * out[m] = the angle from u to v in the plane orthogonal to normal (atan2f: tolerance only). */
+int dc_angle_in_plane(const float* u, const float* v, const float* normal, int64_t M, float* out, void* stream);
+/* rotate_around                                         deltaconv/geometry/connection.py:62-76
+ * out[m] = v turned about axis by angle[m] (sincosf: tolerance only); out [M,3]. */
+int dc_rotate_around(const float* v, const float* axis, const float* angle, int64_t M, float* out, void* stream);
+/* Sum of the neighbours' vectors brought into the centre's frame -- what the reference composes from build_transport
+ * (connection.py:40-47, one matrix per edge) and a scatter over edge_index[0]; no call site of its own in the models.
+ * Vector rows as in dc_apply_div: rows 2i, 2i+1 of v / out are the two components at point i.  coef [n*k,4] (16-byte
+ * aligned) holds one connection per edge.  out[2i+a,c] = scale * acc_a with acc_a = +0, then for slots s ascending,
+ * j = nbr[i,s]: acc_a = (acc_a + coef[i,s,a,0] * v[2j,c]) + coef[i,s,a,1] * v[2j+1,c], every operation rounded to fp32.
+ * The backward runs over the CSC (dc_csc_build), in-edges e = i*k + s ascending:
+ * dv_b = (dv_b + coef[e,0,b] * g[2i,c]) + coef[e,1,b] * g[2i+1,c], dv[2j+b,c] (+)= scale * dv_b.  No atomics. */
+int dc_transport_sum(const int32_t* nbr, int32_t n, int32_t k, const float* coef, const float* v, int32_t C, int64_t ldv,
+                     float scale, float* out, int64_t ldo, void* stream);
+int dc_transport_sum_backward(const int32_t* tptr, const int32_t* tedge, int32_t n, int32_t k, const float* coef,
+                              const float* g, int32_t C, int64_t ldg, float scale, float* dv, int64_t ldv,
+                              int32_t accumulate, void* stream);
+
 /* ---- scalar / vector MLP stream around the dense GEMM -------------------------------------------
  * Linear -> BatchNorm1d(over rows) -> LeakyReLU(0.2)   deltaconv/nn/mlp.py:7-11, nn/nonlin.py:11-35
  * Linear -> VectorNonLin(BatchNorm1d)                  deltaconv/nn/mlp.py:13-17, nn/nonlin.py:38-86
