@@ -18,13 +18,21 @@ points of a shape, or on a mesh's vertices.
     prop = Propagator(train, full, k=3, differentiable=True)            # a loss on ALL points of a shape trains the network
     loss = F.cross_entropy(prop.apply(logits, (c0, c1)), full.y_point[t0:t1])
 
+    prop = Propagator(test, full, k=3, frames="normals")                 # the vector stream: tangent-vector features [2N, C]
+    full_vectors = prop.apply_vectors(vectors)                           # carried into every target point's own frame
+
 Inference only by default; ``differentiable=True`` adds the gradient w.r.t. the propagated VALUES (an ordered, atomics-free sum:
 bit-reproducible).  Positions are never differentiated.  There is no CPU path.
+
+``frames=`` adds the vector stream (csrc/interp_transport.hip: ``dc_knn_cross_transport`` once per dataset,
+``dc_knn_interpolate_vectors`` per use, ``dc_knn_interpolate_vectors_backward`` per backward): tangent-vector features are carried
+into the target point's frame by parallel transport before they are weighted (``geometry.vector_interpolate``).
 """
 import numpy as np
 import torch
 
 from .geometry.interpolate import MAX_K, _InterpolateRows, interpolate_rows, knn_cross, knn_cross_transpose
+from .geometry.vector_interpolate import _InterpolateVectors, interpolate_vectors, knn_cross_transport
 
 __all__ = ["Propagator", "target_view"]
 
@@ -61,9 +69,20 @@ class Propagator:
     the store-wide transposed lists once (``knn_cross_transpose``: per valid slot an int64 edge id and an fp32 coefficient, i.e.
     at most 12 k further bytes per target row, plus 8 bytes per source row of list offsets), and ``apply`` joins the autograd
     graph when ``values`` requires grad and grad mode is on: the backward is one launch of an ordered sum over those lists, no
-    atomics, the same bits on every run.  There is no gradient for positions."""
+    atomics, the same bits on every run.  There is no gradient for positions.
 
-    def __init__(self, source, target, k=3, clouds_per_launch=4096, differentiable=False):
+    ``frames`` (keyword only; default ``None``: nothing further is allocated or launched, and ``apply_vectors`` raises) adds the
+    vector stream.  Either a pair ``(source_frames, target_frames)`` over the stores' rows -- ``source_frames = (normal,
+    x_basis[, y_basis])``, ``target_frames = (normal, x_basis, y_basis)`` -- or ``"normals"``: both derived from the stores'
+    normals through ``build_tangent_basis`` (``source.norm``; ``target.norm`` of a ``DeviceDataset``, ``target.vertex_normals()``
+    of a mesh store; ``ValueError`` where a store has none).  The constructor then builds the store-wide table of per-slot
+    matrices once (``knn_cross_transport``: 16 k bytes per target row), and ``apply_vectors(values, clouds)`` interpolates
+    ``[2 x source rows, C]`` tangent-vector features to ``[2 x target rows, C]``, every neighbour's vector carried into the
+    target's frame first.  The table is built from STORE frames: it matches a network that was fed the store's un-augmented
+    normals.  A rotated or jittered batch has other frames and needs the tensor-level call
+    (``geometry.knn_interpolate_vectors``) with the batch's own.  Frames are never differentiated."""
+
+    def __init__(self, source, target, k=3, clouds_per_launch=4096, differentiable=False, *, frames=None):
         k, per = int(k), int(clouds_per_launch)
         if not 1 <= k <= MAX_K:
             raise ValueError(f"Propagator: k = {k} outside [1, {MAX_K}]")
@@ -95,7 +114,40 @@ class Propagator:
             self.differentiable = bool(differentiable)
             self.lists = knn_cross_transpose(self.idx, self.d2, tptr, self.sptr, num_ref=int(self.soff[-1])) \
                 if self.differentiable else None
+        # (outside no_grad: a frame that requires grad raises, as everywhere in geometry.connection)
+        self.tmat = None if frames is None else self._build_table(frames)
         self._ranges = {}
+
+    def _build_table(self, frames):
+        """The store-wide table of ``c * R`` per slot (``knn_cross_transport``)."""
+        from .geometry import build_tangent_basis
+        if isinstance(frames, str):
+            if frames != "normals":
+                raise ValueError(f"Propagator: frames must be (source_frames, target_frames) or 'normals', got {frames!r}")
+            tnorm = self.target.vertex_normals() if hasattr(self.target, "vertex_normals") else getattr(self.target, "norm", None)
+            snorm = getattr(self.source, "norm", None)
+            if snorm is None or tnorm is None:
+                raise ValueError("Propagator: frames='normals' needs normals on both stores; the "
+                                 f"{'source' if snorm is None else 'target'} has none")
+            sframes, tframes = (snorm,) + tuple(build_tangent_basis(snorm)), (tnorm,) + tuple(build_tangent_basis(tnorm))
+        else:
+            try:
+                sframes, tframes = frames
+                sframes, tframes = tuple(sframes), tuple(tframes)
+            except (TypeError, ValueError):
+                raise ValueError("Propagator: frames must be (source_frames, target_frames) or 'normals'") from None
+        rows, srows = int(self.toff[-1]), int(self.soff[-1])
+        if len(tframes) != 3 or len(sframes) not in (2, 3):
+            raise ValueError("Propagator: source_frames = (normal, x_basis[, y_basis]), target_frames = (normal, x_basis, y_basis)")
+        for name, fr, n in (("source", sframes[:2], srows), ("target", tframes, rows)):
+            for t in fr:
+                if not torch.is_tensor(t) or tuple(t.shape) != (n, 3):
+                    got = tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+                    raise ValueError(f"Propagator: every {name} frame tensor must be [{n}, 3] (the store's rows), got {got}")
+        # one call for the store (a launch per 65 535 clouds): the grid is sized by the largest target cloud, workgroups past a
+        # cloud's end return at once
+        mq = int(self.tsizes.max()) if len(self) else 0
+        return knn_cross_transport(self.idx, self.d2, self.tptr, self.sptr, tframes, sframes, max_query_cloud=mq)
 
     def __len__(self):
         return len(self.tsizes)
@@ -137,6 +189,32 @@ class Propagator:
                                           t1 - t0, t0, True)
         with torch.no_grad():
             return interpolate_rows(values, q, s, self.idx[t0:t1], self.d2[t0:t1], mq, n_query=t1 - t0, out=out)
+
+    def apply_vectors(self, values, clouds=None, out=None):
+        """Tangent-vector features: values DEVICE fp32 ``[2 x source rows of the clouds, C]`` (rows 2i, 2i+1 = the coefficients at
+        source point i in ITS frame; rows may be strided) -> fp32 ``[2 x target rows of those clouds, C]`` in the targets' frames.
+        Needs ``frames=`` at construction.  One launch; no synchronise.  On a ``differentiable`` propagator a ``values`` that
+        requires grad (grad mode on) gives a result on the autograd graph exactly as ``apply`` does -- the same forward bits, the
+        backward one launch over the store-wide lists; ``out`` cannot be combined with that."""
+        if self.tmat is None:
+            raise RuntimeError("Propagator.apply_vectors: this propagator was built without frames= (no transport table)")
+        clouds = (0, len(self)) if clouds is None else clouds
+        c0, c1 = int(clouds[0]), int(clouds[1])
+        q, s, _, (t0, t1), (s0, s1) = self.cloud_range((c0, c1))
+        if values.dim() != 2 or values.shape[0] != 2 * (s1 - s0):
+            raise ValueError(f"Propagator.apply_vectors: values must hold two rows for each of the {s1 - s0} source rows of clouds "
+                             f"{(c0, c1)}, got {tuple(values.shape)}")
+        mq = int(self.tsizes[c0:c1].max()) if c1 > c0 else 0
+        tmat = self.tmat[t0 * self.k:t1 * self.k]
+        if self.differentiable and values.requires_grad and torch.is_grad_enabled():
+            if out is not None:
+                raise ValueError("Propagator.apply_vectors: out= cannot receive a result that is recorded by autograd")
+            mr = int(self.ssizes[c0:c1].max()) if c1 > c0 else 0
+            tptr, tedge, _ = self.lists
+            # store-wide lists, the range's slice of the table: edge e of the store is entry e - t0 * k of the slice (edge_base)
+            return _InterpolateVectors.apply(values, q, s, self.idx[t0:t1], tmat, tptr[s0:s1 + 1], tedge, mq, mr, t1 - t0, t0, True)
+        with torch.no_grad():
+            return interpolate_vectors(values, q, s, self.idx[t0:t1], tmat, mq, n_query=t1 - t0, out=out)
 
     @torch.no_grad()
     def labels(self, pred, clouds=None):

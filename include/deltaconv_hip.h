@@ -926,6 +926,55 @@ int dc_knn_interpolate_backward(const float* g, int64_t ldg, int64_t num_g_rows,
                                 int64_t max_ref_cloud, int32_t k, const int64_t* tptr, const int64_t* tedge, const float* tcoef,
                                 int64_t num_edges, int64_t edge_base, float* dx, int64_t ldx, void* stream);
 
+/* ---- tangent-vector features between two clouds by parallel transport (csrc/interp_transport.hip, csrc/interp_transport_math.h) -- */
+/* Stands in for build_transport (deltaconv/geometry/connection.py:6-47) composed with torch_geometric.nn.knn_interpolate, first
+ * half: the table of per-slot matrices of a dc_knn_cross result.  Entry e = q * k + s (q the ABSOLUTE query row, the row of idx / d2)
+ * is M = c * R, four fp32 products: c the interpolation coefficient of the slot (the tcoef of dc_knn_cross_transpose: w_s / den in
+ * the forward's den bits, exactly 1.0f for the only valid slot of a query, which keeps R's bits) and R the connection of
+ * dc_build_transport from the source frame (sn, sx)[rptr[b] + idx[e]] into the target frame (tn, tx, ty)[q].  A slot with idx
+ * outside [0, size of the reference cloud) holds four +0.0f and indexes nothing.
+ *   qptr, rptr  DEVICE [B+1] ABSOLUTE row offsets, as in dc_knn_cross; tn, tx, ty DEVICE [num_query,3] fp32 rows indexed like idx;
+ *               sn, sx DEVICE [*,3] fp32 rows indexed by the rows rptr names
+ *   num_query   HOST: the rows of idx / d2 / tmat (>= qptr[B]); max_query_cloud HOST, >= the largest query cloud: it sizes the
+ *               grid only (chunks of 256 slots x cloud pairs)
+ *   tmat        DEVICE [num_query * k, 4] fp32, 16-byte aligned; rows of queries outside every pair are not written
+ * None of it is differentiated.  B above 65 535, k outside 1 .. 16, num_query or max_query_cloud outside [0, 2^35), a null pointer
+ * or a misaligned tmat: DC_ERR_ARG with a message, checked before anything touches the device; B = 0, num_query = 0 or
+ * max_query_cloud = 0 returns DC_OK.  One launch, one thread and one 16-byte store per slot, stream-ordered, no allocation, no
+ * synchronisation, no atomics, capturable. */
+int dc_knn_cross_transport(const int64_t* qptr, const int64_t* rptr, int32_t B, int64_t num_query, int64_t max_query_cloud, int32_t k,
+                           const int32_t* idx, const float* d2, const float* tn, const float* tx, const float* ty, const float* sn,
+                           const float* sx, int32_t non_oriented, float* tmat, void* stream);
+/* build_transport (connection.py:6-47) composed with torch_geometric.nn.knn_interpolate, second half: the transported, weighted sum
+ * on the table of dc_knn_cross_transport.  Vector rows as in dc_transport_sum: rows 2i, 2i+1 are the two coefficients at point i.
+ * For query row q of pair b: au = av = +0, then for slots s = 0 .. k-1 in order, invalid ones (idx outside the reference cloud)
+ * skipped, j = rptr[b] + idx[q,s]: au = (au + M00 * v[2j,c]) + M01 * v[2j+1,c], av = (av + M10 * v[2j,c]) + M11 * v[2j+1,c], every
+ * operation rounded to fp32 (the order of dc_transport_sum); out[2q,c] = au, out[2q+1,c] = av.  No valid slot: zeros.
+ *   v           DEVICE [*,ldv] fp32, two rows per reference point, C <= ldv; out DEVICE [*,ldo] fp32, two rows per query, C <= ldo
+ *   qptr, rptr, max_query_cloud, k, idx   as in dc_knn_interpolate (the same grid); tmat 16-byte aligned, indexed like idx
+ * 16-byte loads / stores where the base pointer and the leading dimension allow, scalar otherwise: any C >= 1, the same bits.
+ * The argument checks of dc_knn_interpolate, and a misaligned tmat: DC_ERR_ARG.  One launch, no atomics, capturable. */
+int dc_knn_interpolate_vectors(const float* v, int64_t ldv, int32_t C, const int64_t* qptr, const int64_t* rptr, int32_t B,
+                               int64_t max_query_cloud, int32_t k, const int32_t* idx, const float* tmat, float* out, int64_t ldo,
+                               void* stream);
+/* The gradient of dc_knn_interpolate_vectors w.r.t. v -- what autograd records for build_transport (connection.py:6-47) composed
+ * with torch_geometric.nn.knn_interpolate is an index_add_ with floating-point atomics -- on the lists of dc_knn_cross_transpose
+ * (tptr, tedge; its tcoef is not needed, M carries the coefficient).  For reference row r: du = dw = +0, then for every in-edge e
+ * of r in ascending order, i = e / k - edge_base, M = tmat[e - edge_base * k]: du = (du + M00 * g[2i,c]) + M10 * g[2i+1,c],
+ * dw = (dw + M01 * g[2i,c]) + M11 * g[2i+1,c]; dv[2r,c] = du, dv[2r+1,c] = dw.  Every reference row of every pair is written.
+ *   g           DEVICE [2 * num_g_rows, ldg] fp32; an edge whose query row falls outside [0, num_g_rows) or whose table entry falls
+ *               outside [0, tmat_rows) is skipped
+ *   rptr, max_ref_cloud, tptr, tedge, num_edges, edge_base   as in dc_knn_interpolate_backward (the same grid)
+ *   tmat        DEVICE [tmat_rows, 4] fp32, 16-byte aligned: the table from the call's first query row on (a slice of a store-wide
+ *               table for a range of clouds)
+ *   dv          DEVICE [*, ldv] fp32, two rows per reference point, C <= ldv
+ * The argument checks of dc_knn_interpolate_backward, a negative tmat_rows and a misaligned tmat: DC_ERR_ARG.  One launch, no
+ * atomics, the same bits on every run, capturable. */
+int dc_knn_interpolate_vectors_backward(const float* g, int64_t ldg, int64_t num_g_rows, int32_t C, const int64_t* rptr, int32_t B,
+                                        int64_t max_ref_cloud, int32_t k, const int64_t* tptr, const int64_t* tedge,
+                                        int64_t num_edges, int64_t edge_base, const float* tmat, int64_t tmat_rows, float* dv,
+                                        int64_t ldv, void* stream);
+
 /* ---- per-vertex normals of a store of triangle meshes (csrc/mesh_normal.hip, csrc/mesh_normal_math.h) --------------------------- */
 /* First half of what replaces GenerateMeshNormals() in the reference's ShapeSeg pre_transform (experiments/train_shapeseg.py:31,
  * torch_geometric's transform: an index_add_ of the face normals onto their corners): the vertex-to-incident-corner lists of a whole
