@@ -82,7 +82,10 @@ struct GemmP {
     float* C; long ldc;
     long M; int N; long K;
     int tiles_n, remap, accumulate;
-    long k_per_slab, slab_stride;          // split reduction: blockIdx.y = slab, C += slab * slab_stride
+    int store_y;                           // EPI_VNSTATS only: C receives y[M, N/2] = vn_combine of the (P, Q) pairs (store section).
+                                           // (Sits in the padding in front of k_per_slab: no other field moves, and only EPI_VNSTATS
+                                           //  kernels read it -- the code objects of every other instantiation stay what they were.)
+    long k_per_slab, slab_stride;         // split reduction: blockIdx.y = slab, C += slab * slab_stride
     // BatchNorm-backward prologue (PRO): the A operand is dh = bn_act_backward(dy, h), formed while staging:
     //   dz = dy * (c_sc h + c_sh > 0 ? 1 : slope);   dh = c_g dz + c_a h + c_b     (dc_bn_act_backward_reduce)
     const float* A2; long lda2;            // h, same shape / layout as A (= dy)
@@ -783,32 +786,90 @@ __device__ __forceinline__ void gemm_body(const GemmP& p, const unsigned bid, co
                 stg[(i * 32 + (q & 3) + 8 * (q >> 2) + 4 * lh) * WN + jn * 32 + li] = acc[i][jn][q];
     __syncthreads();
     float* cbase = p.C + (long)blockIdx.y * p.slab_stride;
-    constexpr int RL = WN / 4;                         // lanes per output row
+    if (EPI == EPI_VNSTATS && p.store_y) {
+        // Combined store (first block of a VectorMLP): C = y[M, N/2], (y_u, y_v) = vn_combine of the staged (P, Q) pairs --
+        // the same subtract / add of the same floats as dc_vn_* (combine = 2) apply to a stored PQ, so the same bits.  A lane
+        // takes the row pair (2 rp, 2 rp + 1) = (u, v) and eight staged columns = four (P_c, Q_c) pairs and writes 16 bytes
+        // to each of the two rows of y.  m0, wm0, n0, wn0 are even: no pair straddles a wave.
+        // LDS banks (tools/vn_store_y_lds_sim.py): the staging rows are WN floats, so with every lane starting on the first
+        // 16-byte half of its columns a ds_read_b128 lane group would touch only the even slots of the 256-byte bank row
+        // (2-way at WN = 64, 4-way at WN = 32).  Odd row pairs therefore read their two halves in the opposite order:
+        // conflict-free at WN = 64 (128-column tiles, every hot shape), 2-way at WN = 32, which is left at that.
+        constexpr int PL = WN / 8;                     // lanes per row pair
+        const int ny = p.N / 2;
 #pragma unroll
-    for (int it = 0; it < WM * WN / 4 / 64; ++it) {
-        const int idx = it * 64 + lane;
-        const int r = idx / RL, c4 = (idx % RL) * 4;
-        const long row = m0 + wm0 + r;
-        const int col = n0 + wn0 + c4;
-        f32x4 v = *reinterpret_cast<const f32x4*>(stg + r * WN + c4);
-        float* dst = cbase + row * p.ldc + col;
-        if (FAST) {
-            if (p.accumulate) {
-                const f32x4 o = *reinterpret_cast<const f32x4*>(dst);
-                v += o;
+        for (int it = 0; it < WM * WN / 16 / 64; ++it) {
+            const int idx = it * 64 + lane;
+            const int rp = idx / PL, c8 = (idx % PL) * 8;
+            const bool odd = rp & 1;
+            const float* su = stg + (2 * rp) * WN + c8 + (odd ? 4 : 0);
+            const float* sv = su + WN;
+            const f32x4 ua = *reinterpret_cast<const f32x4*>(su), va = *reinterpret_cast<const f32x4*>(sv);
+            const f32x4 ub = *reinterpret_cast<const f32x4*>(su + (odd ? -4 : 4));
+            const f32x4 vb = *reinterpret_cast<const f32x4*>(sv + (odd ? -4 : 4));
+            float au[2], av[2], bu[2], bv[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                dcnn::vn_combine(ua[2 * j], ua[2 * j + 1], va[2 * j], va[2 * j + 1], au[j], av[j]);
+                dcnn::vn_combine(ub[2 * j], ub[2 * j + 1], vb[2 * j], vb[2 * j + 1], bu[j], bv[j]);
             }
-            dc_store16<DC_ST_GEMM>(dst, v);
-        } else if (row < p.M) {
-            if (col + 3 < p.N && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+            f32x4 yu, yv;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                yu[j] = odd ? bu[j] : au[j]; yu[2 + j] = odd ? au[j] : bu[j];
+                yv[j] = odd ? bv[j] : av[j]; yv[2 + j] = odd ? av[j] : bv[j];
+            }
+            const long row = m0 + wm0 + 2 * rp;
+            const int col = (n0 + wn0) / 2 + c8 / 2;
+            float* du = cbase + row * p.ldc + col;
+            float* dv = du + p.ldc;
+            if (FAST) {
+                dc_store16<DC_ST_GEMM>(du, yu);
+                dc_store16<DC_ST_GEMM>(dv, yv);
+            } else {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    float* dst = h ? dv : du;
+                    const f32x4 v = h ? yv : yu;
+                    if (row + h >= p.M) continue;
+                    if (col + 3 < ny && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+                        dc_store16<DC_ST_GEMM>(dst, v);
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (col + e < ny) dst[e] = v[e];
+                    }
+                }
+            }
+        }
+    } else {
+        constexpr int RL = WN / 4;                         // lanes per output row
+#pragma unroll
+        for (int it = 0; it < WM * WN / 4 / 64; ++it) {
+            const int idx = it * 64 + lane;
+            const int r = idx / RL, c4 = (idx % RL) * 4;
+            const long row = m0 + wm0 + r;
+            const int col = n0 + wn0 + c4;
+            f32x4 v = *reinterpret_cast<const f32x4*>(stg + r * WN + c4);
+            float* dst = cbase + row * p.ldc + col;
+            if (FAST) {
                 if (p.accumulate) {
                     const f32x4 o = *reinterpret_cast<const f32x4*>(dst);
                     v += o;
                 }
                 dc_store16<DC_ST_GEMM>(dst, v);
-            } else {
+            } else if (row < p.M) {
+                if (col + 3 < p.N && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+                    if (p.accumulate) {
+                        const f32x4 o = *reinterpret_cast<const f32x4*>(dst);
+                        v += o;
+                    }
+                    dc_store16<DC_ST_GEMM>(dst, v);
+                } else {
 #pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (col + e < p.N) dst[e] = p.accumulate ? dst[e] + v[e] : v[e];
+                    for (int e = 0; e < 4; ++e)
+                        if (col + e < p.N) dst[e] = p.accumulate ? dst[e] + v[e] : v[e];
+                }
             }
         }
     }
@@ -980,9 +1041,13 @@ thread_local BHint g_bhint = {nullptr, nullptr, 0, 0, 0};
 
 int run_gemm(const char* name, int bl, int epi, const float* A, long lda, const float* B, long ldb, long M, int N, int K,
              float* C, long ldc, int accumulate, int tile, double* part, int stat_cols, hipStream_t s,
-             const Prologue* pro = nullptr) {
+             const Prologue* pro = nullptr, int store_y = 0) {
     BHint hint = g_bhint;
     g_bhint = BHint{nullptr, nullptr, 0, 0, 0};
+    if (store_y && (epi != EPI_VNSTATS || accumulate)) {       // the combined store overwrites, and only (P, Q) pairs combine
+        dc_set_error("%s: the combined store needs the interleaved vector epilogue and accumulate == 0", name);
+        return DC_ERR_ARG;
+    }
     if (hint.src != static_cast<const void*>(B)) hint.p = nullptr;
     // (round 4 lab: N = q * 128 + 64 output columns as two launches -- q * 128 columns on 128-column split tiles + 64 on 64-column
     //  tiles -- is 27 us faster in isolation for 32768 x 448 x 1024 and 8 us SLOWER inside the step, same-box A/B: not used)
@@ -994,6 +1059,7 @@ int run_gemm(const char* name, int bl, int epi, const float* A, long lda, const 
     p.tiles_n = (N + t.bn - 1) / t.bn;
     p.remap = dc_option(DC_OPT_XCD_REMAP);
     p.accumulate = accumulate;
+    p.store_y = store_y;
     p.k_per_slab = K; p.slab_stride = 0;
     p.part = part; p.chunks = (int)tiles_m; p.stat_cols = stat_cols;
     p.A2 = nullptr; p.lda2 = 0; p.pc = nullptr; p.pcn = 0; p.slope = 0.f;
@@ -1122,6 +1188,7 @@ int dc_tn_lds_launch(const float* A, long lda, const float* B, long ldb, long R,
     p.tiles_n = (N + t.bn - 1) / t.bn;
     p.remap = 0;                       // tiles x slabs: every workgroup streams its own rows, nothing to co-locate
     p.accumulate = 0;
+    p.store_y = 0;
     p.k_per_slab = pl.rows_per_slab; p.slab_stride = (long)M * ldpart;
     p.part = nullptr; p.chunks = 0; p.stat_cols = 0;
     p.A2 = h; p.lda2 = ldh; p.pc = coefs; p.pcn = M; p.slope = slope;
@@ -1213,7 +1280,9 @@ DC_EXPORT int dc_linear_bn_stats_forward(const float* X, int64_t ldx, const floa
 
 // Linear + VectorNonLin statistics (nn/nonlin.py:63-79).  interleaved != 0: PQ[2n, 2co] = V[2n, K] Wst[2co, K]^T with
 // interleaved (P_c, Q_c) columns, statistics of |y| over the n points, (y_u, y_v) = (P_u - Q_v, P_v + Q_u) -- what
-// dc_vn_stats(combine = 2) computes from PQ (first block of a VectorMLP, the I_J fold).  interleaved == 0:
+// dc_vn_stats(combine = 2) computes from PQ (first block of a VectorMLP, the I_J fold).  interleaved == 2: the same product and
+// statistics, but PQ receives the combined y[2n, co] (ldpq >= co) -- the bits dc_vn_*(combine = 2) rebuild from a stored PQ, at half
+// the bytes; its consumers take it with combine = 0 (dc_vn_backward*: 3, which still writes the interleaved d(P, Q)).  interleaved == 0:
 // Y[2n, co] = V[2n, K] W[co, K]^T, statistics of |(Y_2i, Y_2i+1)| -- dc_vn_stats(combine = 0) (deeper blocks).
 DC_EXPORT int dc_linear_vn_stats_forward(const float* V, int64_t ldv, const float* Wst, int64_t ldw, int64_t n,
                                          int32_t co, int32_t K, float* PQ, int64_t ldpq, int32_t interleaved,
@@ -1224,7 +1293,8 @@ DC_EXPORT int dc_linear_vn_stats_forward(const float* V, int64_t ldv, const floa
     DC_REQUIRE(V && Wst && PQ && mean && invstd && scale && shift, "dc_linear_vn_stats_forward: null pointer");
     const long M = 2 * n;
     const int N = interleaved ? 2 * co : co;
-    DC_REQUIRE(n >= 1 && co >= 1 && K >= 1 && ldv >= K && ldw >= K && ldpq >= N, "dc_linear_vn_stats_forward: bad size");
+    DC_REQUIRE(n >= 1 && co >= 1 && K >= 1 && ldv >= K && ldw >= K && ldpq >= (interleaved == 2 ? co : N),
+               "dc_linear_vn_stats_forward: bad size");
     if (!workspace || workspace_bytes < dc_linear_stats_workspace_bytes(M, N, K, tile)) {
         dc_set_error("dc_linear_vn_stats_forward: workspace too small");
         return DC_ERR_WORKSPACE;
@@ -1232,7 +1302,7 @@ DC_EXPORT int dc_linear_vn_stats_forward(const float* V, int64_t ldv, const floa
     hipStream_t s = static_cast<hipStream_t>(stream);
     double* part = static_cast<double*>(workspace);
     if (int rc = run_gemm("dc_linear_vn_stats_forward", B_NK, interleaved ? EPI_VNSTATS : EPI_VNSTATS0, V, ldv, Wst, ldw, M,
-                          N, K, PQ, ldpq, 0, tile, part, co, s))
+                          N, K, PQ, ldpq, 0, tile, part, co, s, nullptr, interleaved == 2))
         return rc;
     const dccol::BnFin fin{(long)n, gamma, beta, eps, momentum, running_mean, running_var, mean, invstd, scale, shift};
     hipLaunchKernelGGL((dccol::colreduce_final_kernel<dccol::BnFin>), dim3(co), dim3(64), 0, s, part,
@@ -1268,7 +1338,8 @@ DC_EXPORT int dc_linear_vn_sums_forward(const float* V, int64_t ldv, const float
     DC_REQUIRE(V && Wst && PQ && sums, "dc_linear_vn_sums_forward: null pointer");
     const long M = 2 * n;
     const int N = interleaved ? 2 * co : co;
-    DC_REQUIRE(n >= 1 && co >= 1 && K >= 1 && ldv >= K && ldw >= K && ldpq >= N, "dc_linear_vn_sums_forward: bad size");
+    DC_REQUIRE(n >= 1 && co >= 1 && K >= 1 && ldv >= K && ldw >= K && ldpq >= (interleaved == 2 ? co : N),
+               "dc_linear_vn_sums_forward: bad size");
     if (!workspace || workspace_bytes < dc_linear_stats_workspace_bytes(M, N, K, tile)) {
         dc_set_error("dc_linear_vn_sums_forward: workspace too small");
         return DC_ERR_WORKSPACE;
@@ -1276,7 +1347,7 @@ DC_EXPORT int dc_linear_vn_sums_forward(const float* V, int64_t ldv, const float
     hipStream_t s = static_cast<hipStream_t>(stream);
     double* part = static_cast<double*>(workspace);
     if (int rc = run_gemm("dc_linear_vn_sums_forward", B_NK, interleaved ? EPI_VNSTATS : EPI_VNSTATS0, V, ldv, Wst, ldw, M, N, K, PQ,
-                          ldpq, 0, tile, part, co, s))
+                          ldpq, 0, tile, part, co, s, nullptr, interleaved == 2))
         return rc;
     hipLaunchKernelGGL((dccol::colreduce_final_kernel<dccol::SumsFin>), dim3(co), dim3(64), 0, s, part, chunks_for(M, N, K, tile), co,
                        dccol::SumsFin{sums, co, (double)n});

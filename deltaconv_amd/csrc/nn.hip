@@ -46,6 +46,10 @@ struct BnBwdF {  // dz, dz*xhat
 // vector block: "row" = point i; input rows 2i, 2i+1 of pq.  combine 1: [P | Q] blocked (2*co columns);
 // combine 2: P and Q interleaved (column 2c = P_c, 2c+1 = Q_c) -- what `v_cat @ W.view(2co, K)^T` produces
 // from the reference's [co, 2K] weight without re-stacking it.
+// combine 3 (backward entry points only): `in` is the combined y[2n, co] that dc_linear_vn_stats_forward(interleaved = 2)
+// stored -- loaded as combine 0 -- while the gradient still leaves as the interleaved d(P, Q) [2n, 2co] of combine 2,
+// the operand of the block's two gradient products.
+__host__ __device__ inline int vn_load_code(int combine) { return combine == 3 ? 0 : combine; }
 template <int V>
 __device__ __forceinline__ void vn_load_y(const float* in, long ld, long i, int c0, int co, int combine, FV<V>& yu,
                                           FV<V>& yv) {
@@ -200,14 +204,14 @@ struct VnBwdBody {
     }
     __device__ void row(long i, int c0) {
         FV<V> yu, yv, gu, gv;
-        vn_load_y<V>(in, ld, i, c0, co, combine, yu, yv);
+        vn_load_y<V>(in, ld, i, c0, co, vn_load_code(combine), yu, yv);
         const FV<V> du = ldv<V>(dout + (2 * i) * lddo + c0), dv = ldv<V>(dout + (2 * i + 1) * lddo + c0);
 #pragma unroll
         for (int j = 0; j < V; ++j)
             vn_bwd_dy(yu.v[j], yv.v[j], du.v[j], dv.v[j], sc[j], sh[j], mu[j], is[j], gi[j], a1[j], a2[j], training,
                       gu.v[j], gv.v[j]);
         // d[P|Q]: row u = [dy_u | dy_v], row v = [dy_v | -dy_u]   (transpose of vn_combine)
-        if (combine == 2) {                      // interleaved pairs (dP_c, dQ_c)
+        if (combine == 2 || combine == 3) {      // interleaved pairs (dP_c, dQ_c)
             float eu[2 * V], ev[2 * V];
 #pragma unroll
             for (int j = 0; j < V; ++j) {
@@ -619,23 +623,26 @@ DC_EXPORT int dc_vn_apply(const float* in, int64_t n, int32_t co, int64_t ld, in
     return DC_OK;
 }
 
-// Backward of dc_vn_apply (+ its statistics when training != 0): din has the shape of `in`.
+// Backward of dc_vn_apply (+ its statistics when training != 0): din has the shape of `in`; combine == 3: in = y[2n, co],
+// din = the interleaved d(P, Q) [2n, 2co] (vn_load_code above).
 DC_EXPORT int dc_vn_backward(const float* dout, int64_t lddo, const float* in, int64_t ld, int32_t combine, int64_t n,
                              int32_t co, const float* scale, const float* shift, const float* mean,
                              const float* invstd, const float* gamma, int32_t training, float* din, int64_t lddi,
                              float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream) {
     DC_REQUIRE(dout && in && scale && shift && mean && invstd && din, "dc_vn_backward: null pointer");
-    DC_REQUIRE(n >= 1 && co >= 1 && lddo >= co && ld >= (combine ? 2 * co : co) && lddi >= (combine ? 2 * co : co),
+    DC_REQUIRE(combine >= 0 && combine <= 3 && n >= 1 && co >= 1 && lddo >= co && ld >= (vn_load_code(combine) ? 2 * co : co) &&
+                   lddi >= (combine ? 2 * co : co),
                "dc_vn_backward: bad size");
     DC_WS_CHECK("dc_vn_backward", n, co)
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Ws w = carve(workspace, n, co);
     const bool v4 = co % 4 == 0 && ld % 4 == 0 && lddo % 4 == 0 && lddi % 4 == 0 && al16(in) && al16(dout) && al16(din);
     const BwdFin fin{(long)n, dgamma, dbeta, w.m1, w.m2};
+    const int lc = vn_load_code(combine);           // the reduction only loads
     if (v4)
-        run_colreduce<4>(VnBwdF<4>{in, dout, scale, shift, mean, invstd, (long)ld, (long)lddo, co, combine}, n, co, w, s, fin);
+        run_colreduce<4>(VnBwdF<4>{in, dout, scale, shift, mean, invstd, (long)ld, (long)lddo, co, lc}, n, co, w, s, fin);
     else
-        run_colreduce<1>(VnBwdF<1>{in, dout, scale, shift, mean, invstd, (long)ld, (long)lddo, co, combine}, n, co, w, s, fin);
+        run_colreduce<1>(VnBwdF<1>{in, dout, scale, shift, mean, invstd, (long)ld, (long)lddo, co, lc}, n, co, w, s, fin);
     if (v4)
         run_tile<4>(VnBwdBody<4>{in, dout, scale, shift, mean, invstd, gamma, w.m1, w.m2, din, (long)ld, (long)lddo,
                                  (long)lddi, co, combine, training}, n, co, s);
@@ -860,15 +867,16 @@ DC_EXPORT int dc_vn_backward_sums(const float* dout, int64_t lddo, const float* 
                                   const float* invstd, double* sums, void* workspace, size_t workspace_bytes,
                                   void* stream) {
     DC_REQUIRE(dout && in && scale && shift && mean && invstd && sums, "dc_vn_backward_sums: null pointer");
-    DC_REQUIRE(n >= 1 && co >= 1 && lddo >= co && ld >= (combine ? 2 * co : co), "dc_vn_backward_sums: bad size");
+    DC_REQUIRE(n >= 1 && co >= 1 && lddo >= co && ld >= (vn_load_code(combine) ? 2 * co : co), "dc_vn_backward_sums: bad size");
     DC_WS_CHECK("dc_vn_backward_sums", n, co)
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Ws w = carve(workspace, n, co);
     const SumsFin fin{sums, co, (double)n};
+    const int lc = vn_load_code(combine);           // the reduction only loads
     if (co % 4 == 0 && ld % 4 == 0 && lddo % 4 == 0 && al16(in) && al16(dout))
-        run_colreduce<4>(VnBwdF<4>{in, dout, scale, shift, mean, invstd, (long)ld, (long)lddo, co, combine}, n, co, w, s, fin);
+        run_colreduce<4>(VnBwdF<4>{in, dout, scale, shift, mean, invstd, (long)ld, (long)lddo, co, lc}, n, co, w, s, fin);
     else
-        run_colreduce<1>(VnBwdF<1>{in, dout, scale, shift, mean, invstd, (long)ld, (long)lddo, co, combine}, n, co, w, s, fin);
+        run_colreduce<1>(VnBwdF<1>{in, dout, scale, shift, mean, invstd, (long)ld, (long)lddo, co, lc}, n, co, w, s, fin);
     DC_CHECK_LAUNCH("dc_vn_backward_sums");
     return DC_OK;
 }
@@ -878,7 +886,8 @@ DC_EXPORT int dc_vn_backward_apply(const float* dout, int64_t lddo, const float*
                                    const float* invstd, const float* gamma, int32_t training, const float* m1,
                                    const float* m2, float* din, int64_t lddi, void* stream) {
     DC_REQUIRE(dout && in && scale && shift && mean && invstd && m1 && m2 && din, "dc_vn_backward_apply: null pointer");
-    DC_REQUIRE(n >= 1 && co >= 1 && lddo >= co && ld >= (combine ? 2 * co : co) && lddi >= (combine ? 2 * co : co),
+    DC_REQUIRE(combine >= 0 && combine <= 3 && n >= 1 && co >= 1 && lddo >= co && ld >= (vn_load_code(combine) ? 2 * co : co) &&
+                   lddi >= (combine ? 2 * co : co),
                "dc_vn_backward_apply: bad size");
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (co % 4 == 0 && ld % 4 == 0 && lddo % 4 == 0 && lddi % 4 == 0 && al16(in) && al16(dout) && al16(din))

@@ -200,12 +200,13 @@ def bn_act_backward(dy, lddy, h, coef, gamma, slope, batch_stats, group, has_g=T
 
 def vn_backward(dout, lddo, h, combine, coef, gamma, batch_stats, group, has_g=True, has_b=True):
     """-> (dh, dgamma, dbeta) of the vector non-linearity on h ([2n, co], or interleaved (P, Q) [2n, 2co] with `combine`) for
-    the incoming dout (row stride lddo); `group` as in bn_act_backward.  (No BatchNorm at all: gamma = None, batch_stats = 0.)"""
+    the incoming dout (row stride lddo); `group` as in bn_act_backward.  (No BatchNorm at all: gamma = None, batch_stats = 0.)
+    combine = 3: h = y[2n, co] of a first block, dh = the interleaved d(P, Q) [2n, 2co] its gradient products consume."""
     ld = h.shape[1]
-    co = ld // 2 if combine else ld
+    co = ld // 2 if combine in (1, 2) else ld
     n = h.shape[0] // 2
     dev = h.device
-    dh = torch.empty_like(h)
+    dh = torch.empty(2 * n, 2 * co, dtype=h.dtype, device=dev) if combine == 3 else torch.empty_like(h)
     dgamma, dbeta = _dgamma_dbeta(co, dev, has_g, has_b)
     ws, nb = _ws(n, co, dev)
     if group is not None:
@@ -214,10 +215,10 @@ def vn_backward(dout, lddo, h, combine, coef, gamma, batch_stats, group, has_g=T
         m = torch.empty(2, co, dtype=torch.float32, device=dev)
         lib.call("dc_sync_means", stats, co, m[0], m[1], dgamma, dbeta)
         lib.call("dc_vn_backward_apply", dout, lddo, h, ld, combine, n, co, coef[2], coef[3], coef[0], coef[1], gamma, 1,
-                 m[0], m[1], dh, ld)
+                 m[0], m[1], dh, dh.stride(0))
     else:
         lib.call("dc_vn_backward", dout, lddo, h, ld, combine, n, co, coef[2], coef[3], coef[0], coef[1], gamma,
-                 int(batch_stats), dh, ld, dgamma, dbeta, ws, nb)
+                 int(batch_stats), dh, dh.stride(0), dgamma, dbeta, ws, nb)
     return dh, dgamma, dbeta
 
 
@@ -865,7 +866,8 @@ def linear_stats(x, w, bn, gamma, beta, vn=0, defer_final=False):
     """h = x w^T together with the BatchNorm coefficients of the layer behind it, from the GEMM epilogue:
     -> (h, coef[4, C] = mean / invstd / scale / shift, use_batch_stats).  vn = 2: w = the [2co, K] view of the first
     vector block, statistics of the per-point norms of the interleaved (P_c, Q_c) output (C = co); vn = 1: a deeper
-    vector block, h = [2n, co], norms over the row pairs.  Running statistics and num_batches_tracked advance exactly
+    vector block, h = [2n, co], norms over the row pairs.  With vn = 2 under batch statistics (and VN_STORE_Y) h is the
+    combined y [2n, co] instead of the pair [2n, 2co]: callers tell the two by h.shape[1].  Running statistics and num_batches_tracked advance exactly
     as in bn_act / vector_nonlin."""
     x, w = _rowmajor(x), _rowmajor(w)
     m, k = x.shape
@@ -876,7 +878,9 @@ def linear_stats(x, w, bn, gamma, beta, vn=0, defer_final=False):
     _require_fp32_gpu("linear_stats", x, w)        # before bn_mode: a refused call leaves the layer's counter and caches alone
     use_batch, mom, rm, rv, eps = bn_mode(bn, rows)
     coef = torch.empty(4, c, dtype=torch.float32, device=dev)
-    h = torch.empty(m, n, dtype=torch.float32, device=dev)
+    # first vector block under batch statistics: the epilogue stores y[2n, co] (interleaved = 2) instead of the (P, Q) pair
+    il = (2 if VN_STORE_Y[0] and use_batch else 1) if vn == 2 else 0
+    h = torch.empty(m, c if il == 2 else n, dtype=torch.float32, device=dev)
     group = sync_group() if use_batch else None
     if group is not None:
         # statistics of the GLOBAL batch (deltaconv_amd/dp.py): the same GEMM epilogue, cut at the reduction -- this rank's fp64
@@ -888,7 +892,7 @@ def linear_stats(x, w, bn, gamma, beta, vn=0, defer_final=False):
         sums = torch.empty(2, 2 * c + 1, dtype=torch.float64, device=dev)      # two records: [0] all-reduced, [1] local
         _hint_planes(w, False)
         if vn:
-            lib.call("dc_linear_vn_sums_forward", x, x.stride(0), w, w.stride(0), rows, c, k, h, n, int(vn == 2), sums, 0, ws, nb)
+            lib.call("dc_linear_vn_sums_forward", x, x.stride(0), w, w.stride(0), rows, c, k, h, h.stride(0), il, sums, 0, ws, nb)
         else:
             lib.call("dc_linear_bn_sums_forward", x, x.stride(0), w, w.stride(0), m, n, k, h, n, sums, 0, ws, nb)
         dp.all_reduce_stats(sums[0], group)
@@ -899,7 +903,7 @@ def linear_stats(x, w, bn, gamma, beta, vn=0, defer_final=False):
         ws = torch.empty((nb + 7) // 8, dtype=torch.float64, device=dev)
         _hint_planes(w, False)
         if vn:
-            lib.call("dc_linear_vn_stats_forward", x, x.stride(0), w, w.stride(0), rows, c, k, h, n, int(vn == 2), gamma,
+            lib.call("dc_linear_vn_stats_forward", x, x.stride(0), w, w.stride(0), rows, c, k, h, h.stride(0), il, gamma,
                      beta, eps, mom, rm, rv, coef[0], coef[1], coef[2], coef[3], 0, ws, nb)
         else:
             if defer_final:
@@ -911,6 +915,8 @@ def linear_stats(x, w, bn, gamma, beta, vn=0, defer_final=False):
     return h, eval_coeffs(gamma, beta, rm, rv, eps, c), False
 
 
+# A/B switch: the first block of a VectorMLP stores the combined y[2n, co] from the GEMM epilogue (1) / the interleaved (P, Q) pair (0)
+VN_STORE_Y = [os.environ.get("DC_VN_STORE_Y", "1") != "0"]
 FUSE_BN_BWD = True     # A/B switch: BatchNorm/activation backward folded into the consuming GEMMs (no dh tensor)
 
 

@@ -257,13 +257,14 @@ class DeltaConvLayerFn(torch.autograd.Function):
             for j, ((W, gv, bv), bn) in enumerate(zip(pv, cfg.bns_v)):
                 c1 = W.shape[0]
                 if j == 0:
-                    # rows (c, half) of the [c1, 2K] weight: the I_J fold, a free view.  Output [2n, 2c1], columns
-                    # interleaved (P_c, Q_c); statistics of the per-point norms from the GEMM epilogue
+                    # rows (c, half) of the [c1, 2K] weight: the I_J fold, a free view.  Statistics of the per-point norms
+                    # from the GEMM epilogue, which also stores the combined y [2n, c1] (fused.VN_STORE_Y); the inference
+                    # branch and the switched-off form return [2n, 2c1], columns interleaved (P_c, Q_c)
                     h, coef, use = fused.linear_stats(inp, W.view(2 * c1, K), bn, gv, bv, vn=2)
                 else:
                     h, coef, use = fused.linear_stats(inp, W, bn, gv, bv, vn=1)
                 out = v_new if j == nv - 1 else torch.empty(2 * n, c1, **f32)
-                call("dc_vn_apply", h, n, c1, h.shape[1], 2 if j == 0 else 0, coef[2], coef[3], out, out.stride(0))
+                call("dc_vn_apply", h, n, c1, h.shape[1], 2 if h.shape[1] != c1 else 0, coef[2], coef[3], out, out.stride(0))
                 saved_v.append((inp, h, coef, use))
                 inp = out
 
@@ -334,7 +335,9 @@ class DeltaConvLayerFn(torch.autograd.Function):
                 inp, h, coef = svv[j]
                 W, gv, _ = pv[j]
                 # (the group the FORWARD statistics were reduced over: fused.BatchStats)
-                dh, dg, db = fused.vn_backward(dcur, ldd, h, 2 if j == 0 else 0, coef, gv, use_v[j], fused.group_of(use_v[j]))
+                # first block: h is y [2n, c1] (code 3: dh still comes out as the interleaved d(P, Q)) or the (P, Q) pair (2)
+                code = (3 if h.shape[1] == W.shape[0] else 2) if j == 0 else 0
+                dh, dg, db = fused.vn_backward(dcur, ldd, h, code, coef, gv, use_v[j], fused.group_of(use_v[j]))
                 if j == 0:
                     Wst = W.view(2 * W.shape[0], K)
                     if need_v or need_x:

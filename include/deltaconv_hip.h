@@ -359,7 +359,10 @@ int dc_bn_act_backward(const float* dy, int64_t lddy, const float* h, int64_t ld
  * I_J(v_cat)) with the weight halves stacked, y_u = P_u - Q_v, y_v = P_v + Q_u
  * (deltaconv/geometry/operators.py:9-21 folded into the epilogue); combine == 0 -> [2n, co] = y;
  * combine == 2 -> P and Q interleaved (column 2c = P_c, 2c+1 = Q_c), i.e. v_cat @ W.view(2co, K)^T for the
- * reference's [co, 2K] weight of the first VectorMLP layer, no re-stacking of W. */
+ * reference's [co, 2K] weight of the first VectorMLP layer, no re-stacking of W.
+ * combine == 3 (dc_vn_backward, dc_vn_backward_sums, dc_vn_backward_apply only): in = y[2n, co] as stored by
+ * dc_linear_vn_stats_forward(interleaved = 2), ld >= co; din = the interleaved d(P, Q) [2n, 2co] of combine == 2
+ * (lddi >= 2co), the operand of the block's gradient products.  Same bits as combine == 2 on the matching PQ. */
 int dc_vn_stats(const float* in, int64_t n, int32_t co, int64_t ld, int32_t combine, const float* gamma,
                 const float* beta, float eps, float momentum, float* running_mean, float* running_var, float* mean,
                 float* invstd, float* scale, float* shift, void* workspace, size_t workspace_bytes, void* stream);
@@ -532,7 +535,12 @@ int dc_gemm_next_b_planes(const void* weight, const void* planes, int64_t plane_
  *   dc_linear_bn_stats_forward  Y = X W^T  + BatchNorm batch statistics of Y (== dc_bn_stats on Y)
  *   dc_linear_vn_stats_forward  interleaved: PQ[2n,2co] = V[2n,K] Wst[2co,K]^T (columns interleaved (P_c, Q_c)) +
  *                               statistics of |y| over the n points (== dc_vn_stats(combine = 2) on PQ); otherwise
- *                               Y[2n,co] = V W[co,K]^T + statistics of |(Y_2i, Y_2i+1)| (== dc_vn_stats(combine = 0))
+ *                               Y[2n,co] = V W[co,K]^T + statistics of |(Y_2i, Y_2i+1)| (== dc_vn_stats(combine = 0)).
+ *                               interleaved == 2: product and statistics of interleaved == 1, but PQ receives the combined
+ *                               y[2n,co] (y_u = P_u - Q_v, y_v = P_v + Q_u; ldpq >= co) -- the bits the dc_vn_* kernels
+ *                               rebuild from a stored PQ with combine = 2, at half the bytes.  Consumers: dc_vn_apply /
+ *                               dc_vn_stats / dc_vn_sums with combine = 0, the dc_vn_backward* family with combine = 3.
+ *                               (dc_linear_vn_sums_forward takes the same three values.)
  * The statistics come out of the GEMM epilogue (fp64 tile sums, ordered final stage): no pass over Y.
  * Workspace: dc_linear_stats_workspace_bytes(M, N, K, tile)  (vn: M = 2n, N = 2co). */
 int dc_linear_forward(const float* X, int64_t ldx, const float* W, int64_t ldw, int64_t M, int32_t N, int32_t K,
