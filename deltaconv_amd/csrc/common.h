@@ -47,6 +47,7 @@ enum { DC_OPT_XCD_REMAP = 0, DC_OPT_GATHER_BATCH = 1, DC_OPT_TN_LDS = 2 /* 2: we
 int dc_option(int key);
 
 static inline int dc_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+inline bool aligned_to(const void* p, int bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
 
 // Output stores ----------------------------------------------------------------------------------------------------
 // A plain store leaves a kernel's output dirty in the per-XCD L2 until the end-of-kernel write-back, which is then

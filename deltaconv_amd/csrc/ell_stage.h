@@ -107,7 +107,6 @@ inline void launch_T(long n, int C, const float* coefT, const int* tptr, const i
                        dc_option(DC_OPT_XCD_REMAP), coefT, tptr, tedge, k, op);
 }
 
-inline bool aligned_to(const void* p, int bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
 // vector width: 16-byte path when channels, strides and bases allow it; 8-byte path for even channel counts / strides /
 // bases (the layer-0 blocks: grad x' sits at column 6 of a 70-float row -- 8-byte loads need half the texture-addresser
 // cycles of dword loads: 38 -> 22 us for that transposed apply); else dword

@@ -91,6 +91,17 @@ struct alignas(16) F4 {
     float v[4];
 };
 
+// The guarded load of a channel group: r [4] = nc values at row (one 16-byte load when vec), zeros behind them.
+DC_HD void load4(const float* row, int nc, bool vec, float* r) {
+    r[0] = r[1] = r[2] = r[3] = 0.f;
+    if (vec) {
+        const F4 t = *reinterpret_cast<const F4*>(row);
+        r[0] = t.v[0]; r[1] = t.v[1]; r[2] = t.v[2]; r[3] = t.v[3];
+    } else {
+        for (int c = 0; c < nc; ++c) r[c] = row[c];
+    }
+}
+
 // Channels c0 .. c0+nc-1 (nc in 1 .. 4) of one query: x [Nr, ldx] the rows of ITS reference cloud, idx / d2 [k] its slots.
 // vec: x + c0 is 16-byte aligned in every row and nc = 4 (one 16-byte load per slot).  out [4] receives nc values.
 DC_HD void interp4(const float* x, long long ldx, long long nr, int k, const int* idx, const float* d2, int c0, int nc, bool vec,
@@ -102,14 +113,8 @@ DC_HD void interp4(const float* x, long long ldx, long long nr, int k, const int
         const long long j = idx[s];
         if (j < 0 || j >= nr) continue;
         const float w = weight(d2[s]);
-        const float* row = x + j * ldx + c0;
-        float r[4] = {0.f, 0.f, 0.f, 0.f};
-        if (vec) {
-            const F4 t = *reinterpret_cast<const F4*>(row);
-            r[0] = t.v[0]; r[1] = t.v[1]; r[2] = t.v[2]; r[3] = t.v[3];
-        } else {
-            for (int c = 0; c < nc; ++c) r[c] = row[c];
-        }
+        float r[4];
+        load4(x + j * ldx + c0, nc, vec, r);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const float p = w * r[c];
@@ -199,15 +204,7 @@ DC_HD void bwd4(const float* g, long long ldg, long long rows, int k, long long 
             gr[u] = g + (in[u] ? row : 0) * ldg + c0;
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            r[u][0] = r[u][1] = r[u][2] = r[u][3] = 0.f;
-            if (vec) {
-                const F4 v = *reinterpret_cast<const F4*>(gr[u]);
-                r[u][0] = v.v[0]; r[u][1] = v.v[1]; r[u][2] = v.v[2]; r[u][3] = v.v[3];
-            } else {
-                for (int ch = 0; ch < nc; ++ch) r[u][ch] = gr[u][ch];
-            }
-        }
+        for (int u = 0; u < U; ++u) load4(gr[u], nc, vec, r[u]);
 #pragma unroll
         for (int u = 0; u < U; ++u)
 #pragma unroll

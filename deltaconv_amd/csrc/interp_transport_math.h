@@ -28,7 +28,7 @@
 namespace dcvinterp {
 using dcconn::R4;
 using dcinterp::add_rn;
-using dcinterp::F4;
+using dcinterp::load4;
 using dcinterp::mul_rn;
 
 DC_HD R4 zero_entry() { return R4{0.f, 0.f, 0.f, 0.f}; }
@@ -54,16 +54,6 @@ DC_HD R4 entry(const int64_t* qptr, const int64_t* rptr, int B, int k, const int
     const int b = dcinterp::pair_of(qptr, B, q);
     if (b < 0) return zero_entry();
     return entry_in_pair(q, (int)(e - q * k), rptr[b], rptr[b + 1] - rptr[b], k, idx, d2, tn, tx, ty, sn, sx, non_oriented);
-}
-
-DC_HD void load4(const float* row, int nc, bool vec, float* r) {
-    r[0] = r[1] = r[2] = r[3] = 0.f;
-    if (vec) {
-        const F4 t = *reinterpret_cast<const F4*>(row);
-        r[0] = t.v[0]; r[1] = t.v[1]; r[2] = t.v[2]; r[3] = t.v[3];
-    } else {
-        for (int c = 0; c < nc; ++c) r[c] = row[c];
-    }
 }
 
 // Channels c0 .. c0+nc-1 (nc in 1 .. 4) of one query: v [2 Nr, ldv] the rows of ITS reference cloud, idx [k] / M [k] its slots.

@@ -12,26 +12,10 @@ with respect to ``v`` only.  There is no CPU path."""
 import torch
 
 from .._lib import lib, require_gpu
+from ._cross import device as _device, no_grad_inputs as _no_grad_inputs, rows3 as _rows3
 from .graph import Graph, _GRAPH_OF
 
 __all__ = ["build_transport", "angle_in_plane", "rotate_around", "build_graph_transport", "transport_sum"]
-
-
-def _no_grad_inputs(fn, **tensors):
-    if torch.is_grad_enabled():
-        for name, t in tensors.items():
-            if torch.is_tensor(t) and t.requires_grad:
-                raise RuntimeError(f"{fn}: {name} requires grad, but the device {fn} is not differentiable (no backward kernel); "
-                                   f"call it under torch.no_grad() or pass {name}.detach()")
-
-
-def _rows3(fn, name, t, m=None):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError(f"{fn}: {name} must be a tensor on a HIP device (there is no CPU path)")
-    if t.dim() != 2 or t.shape[1] != 3 or (m is not None and t.shape[0] != m):
-        want = "[M,3]" if m is None else f"[{m},3]"
-        raise ValueError(f"{fn}: {name} must be {want}, got {tuple(t.shape)}")
-    return t.detach().float().contiguous()
 
 
 def build_transport(target_n, target_x, target_y, source_n, source_x, non_oriented=True):
@@ -71,8 +55,7 @@ def rotate_around(v, axis, angle):
     v = _rows3(fn, "v", v)
     m = v.shape[0]
     axis = _rows3(fn, "axis", axis, m)
-    if not torch.is_tensor(angle) or not angle.is_cuda:
-        raise RuntimeError(f"{fn}: angle must be a tensor on a HIP device (there is no CPU path)")
+    _device(fn, "angle", angle)
     if angle.numel() != m or angle.dim() > 2 or (angle.dim() == 2 and angle.shape[1] != 1):
         raise ValueError(f"{fn}: angle must be [{m}] or [{m},1], got {tuple(angle.shape)}")
     angle = angle.detach().float().reshape(m).contiguous()
@@ -155,8 +138,7 @@ def transport_sum(v, connection, edge_index, weights=None, reduce="sum"):
     if reduce not in ("sum", "add", "mean"):
         raise ValueError(f"{fn}: reduce must be 'sum', 'add' or 'mean', got {reduce!r}")
     _no_grad_inputs(fn, connection=connection, weights=weights)
-    if not torch.is_tensor(v) or not v.is_cuda:
-        raise RuntimeError(f"{fn}: v must be a tensor on a HIP device (there is no CPU path)")
+    _device(fn, "v", v)
     if v.dim() != 2 or v.shape[0] % 2:
         raise ValueError(f"{fn}: v must be [2N,C] (rows 2i, 2i+1 = the two components at point i), got {tuple(v.shape)}")
     if v.dtype != torch.float32:

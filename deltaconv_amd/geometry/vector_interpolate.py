@@ -12,31 +12,16 @@ apply kernels are pure gathers over them.  The gradient w.r.t. the VALUES is opt
 atomics-free sum over the transposed lists of the search (``knn_cross_transpose``), bit-reproducible.  None of the geometry is
 differentiable: frames, normals and positions are constants.  There is no CPU path."""
 import torch
-from torch.autograd.function import once_differentiable
 
-from .connection import _no_grad_inputs, _rows3
-from .interpolate import MAX_K, _device_f32, _launches, _pairs, knn_cross, knn_cross_transpose
+from . import _cross
+from ._cross import MAX_K
+from .interpolate import knn_cross, knn_cross_transpose
 
 __all__ = ["knn_cross_transport", "interpolate_vectors", "interpolate_vectors_backward", "knn_interpolate_vectors"]
 
 
-def _search(fn, idx, d2=None):
-    for name, t, dt in (("idx", idx, torch.int32), ("d2", d2, torch.float32)):
-        if t is None:
-            continue
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise RuntimeError(f"{fn}: {name} must be a tensor on a HIP device (there is no CPU path)")
-        if t.dtype != dt or t.dim() != 2 or not t.is_contiguous():
-            raise ValueError(f"{fn}: {name} must be contiguous {dt} [Nq, k]")
-    if (d2 is not None and idx.shape != d2.shape) or not 1 <= idx.shape[1] <= MAX_K:
-        raise ValueError(f"{fn}: idx {tuple(idx.shape)}" + (f" and d2 {tuple(d2.shape)} must agree," if d2 is not None else ":") +
-                         f" k in [1, {MAX_K}]")
-    return int(idx.shape[0]), int(idx.shape[1])
-
-
 def _table(fn, tmat, rows=None):
-    if not torch.is_tensor(tmat) or not tmat.is_cuda:
-        raise RuntimeError(f"{fn}: tmat must be a tensor on a HIP device (there is no CPU path)")
+    _cross.device(fn, "tmat", tmat)
     if tmat.dtype != torch.float32 or tmat.dim() != 2 or tmat.shape[1] != 4 or not tmat.is_contiguous() or \
             (rows is not None and tmat.shape[0] != rows):
         raise ValueError(f"{fn}: tmat must be contiguous float32 [{'Nq*k' if rows is None else rows}, 4] (knn_cross_transport), got "
@@ -44,37 +29,6 @@ def _table(fn, tmat, rows=None):
     if tmat.data_ptr() % 16:
         raise ValueError(f"{fn}: tmat must be 16-byte aligned (one 16-byte load per slot)")
     return tmat
-
-
-def _values(fn, name, t):
-    """[2n, C] DEVICE rows for the kernels: fp32, unit stride along the channels, rows ld >= C apart (anything else is copied)."""
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError(f"{fn}: {name} must be a tensor on a HIP device (there is no CPU path)")
-    if t.dim() != 2 or t.shape[1] < 1 or t.shape[0] % 2:
-        raise ValueError(f"{fn}: {name} must be [2n, C] with C >= 1 (rows 2i, 2i+1 = the two coefficients at point i), got "
-                         f"{tuple(t.shape)}")
-    if t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        t = t.float().contiguous()
-    return t, int(t.shape[1]), (int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1]))
-
-
-def _out(fn, out, rows, c, device):
-    if out is None:
-        out = torch.zeros((rows, c), dtype=torch.float32, device=device)
-    elif not torch.is_tensor(out) or not out.is_cuda:
-        raise RuntimeError(f"{fn}: out must be a tensor on a HIP device (there is no CPU path)")
-    elif out.dtype != torch.float32 or tuple(out.shape) != (rows, c) or (c > 1 and out.stride(1) != 1) or \
-            (rows > 1 and out.stride(0) < c):
-        raise ValueError(f"{fn}: out must be float32 [{rows}, {c}] with unit stride along the channels and rows that do not overlap")
-    return out, (int(out.stride(0)) if rows > 1 else c)
-
-
-def _offsets_of(fn, device, **ptrs):
-    """int64 [B+1] offsets on the device, each: a list or a host tensor is brought over, as knn_cross_transpose does."""
-    out = [torch.as_tensor(t).to(device=device, dtype=torch.int64).contiguous() for t in ptrs.values()]
-    if any(t.dim() != 1 or t.numel() < 1 or t.shape != out[0].shape for t in out):
-        raise ValueError(f"{fn}: {' and '.join(ptrs)} must hold B+1 offsets each")
-    return out if len(out) > 1 else out[0]
 
 
 def knn_cross_transport(idx, d2, qptr, rptr, query_frames, ref_frames, non_oriented=True, max_query_cloud=None):
@@ -90,26 +44,26 @@ def knn_cross_transport(idx, d2, qptr, rptr, query_frames, ref_frames, non_orien
     raises ``RuntimeError``."""
     from .._lib import lib
     fn = "knn_cross_transport"
-    nq, k = _search(fn, idx, d2)
+    nq, k = _cross.search(fn, idx, d2)
     if len(query_frames) != 3 or len(ref_frames) not in (2, 3):
         raise ValueError(f"{fn}: query_frames = (normal, x_basis, y_basis), ref_frames = (normal, x_basis[, y_basis])")
-    _no_grad_inputs(fn, query_normal=query_frames[0], query_x_basis=query_frames[1], query_y_basis=query_frames[2],
-                    ref_normal=ref_frames[0], ref_x_basis=ref_frames[1], d2=d2)
-    tn = _rows3(fn, "query normal", query_frames[0], nq)
-    tx, ty = _rows3(fn, "query x_basis", query_frames[1], nq), _rows3(fn, "query y_basis", query_frames[2], nq)
-    sn = _rows3(fn, "ref normal", ref_frames[0])
-    sx = _rows3(fn, "ref x_basis", ref_frames[1], sn.shape[0])
+    _cross.no_grad_inputs(fn, query_normal=query_frames[0], query_x_basis=query_frames[1], query_y_basis=query_frames[2],
+                           ref_normal=ref_frames[0], ref_x_basis=ref_frames[1], d2=d2)
+    tn = _cross.rows3(fn, "query normal", query_frames[0], nq)
+    tx, ty = _cross.rows3(fn, "query x_basis", query_frames[1], nq), _cross.rows3(fn, "query y_basis", query_frames[2], nq)
+    sn = _cross.rows3(fn, "ref normal", ref_frames[0])
+    sx = _cross.rows3(fn, "ref x_basis", ref_frames[1], sn.shape[0])
     dev = idx.device
-    qptr, rptr = _offsets_of(fn, dev, qptr=qptr, rptr=rptr)
+    qptr, rptr = _cross.offsets(fn, dev, qptr=qptr, rptr=rptr)
     b = int(qptr.numel()) - 1
-    mq = int(max_query_cloud) if max_query_cloud is not None else (int((qptr[1:] - qptr[:-1]).max()) if b else 0)
+    mq = _cross.largest_cloud(qptr, max_query_cloud)
     with torch.no_grad():
         tmat = torch.zeros((nq * k, 4), dtype=torch.float32, device=dev)
         if nq == 0 or mq == 0:
             return tmat
         if sn.shape[0] == 0:                   # every reference cloud is empty: rows that are never read stand in for the null pointers
             sn, sx = sn.new_zeros((1, 3)), sx.new_zeros((1, 3))
-        for lo, hi in _launches(b):
+        for lo, hi in _cross.launches(b):
             lib.call("dc_knn_cross_transport", qptr[lo:hi + 1], rptr[lo:hi + 1], hi - lo, nq, mq, k, idx, d2, tn, tx, ty, sn, sx,
                      int(bool(non_oriented)), tmat)
     return tmat
@@ -123,18 +77,18 @@ def interpolate_vectors(v, qptr, rptr, idx, tmat, max_query_cloud, n_query=None,
     zeros.  Not recorded by autograd; ``interpolate_vectors_backward`` is its gradient w.r.t. v."""
     from .._lib import lib
     fn = "interpolate_vectors"
-    v, c, ldv = _values(fn, "v", v)
-    nq, k = _search(fn, idx)
+    v, c, ldv = _cross.values(fn, "v", v, per_point=2)
+    nq, k = _cross.search(fn, idx)
     tmat = _table(fn, tmat, nq * k)
-    qptr, rptr = _offsets_of(fn, v.device, qptr=qptr, rptr=rptr)
+    qptr, rptr = _cross.offsets(fn, v.device, qptr=qptr, rptr=rptr)
     n_query = nq if n_query is None else int(n_query)
-    out, ldo = _out(fn, out, 2 * n_query, c, v.device)
+    out, ldo = _cross.out_rows(fn, out, 2 * n_query, c, v.device, on_device=True)
     b = int(qptr.numel()) - 1
     if n_query == 0 or nq == 0:
         return out
     if v.shape[0] == 0:                        # no reference row at all: every slot is invalid, rows that are never read stand in
         v, ldv = v.new_zeros((2, c)), c
-    for lo, hi in _launches(b):
+    for lo, hi in _cross.launches(b):
         lib.call("dc_knn_interpolate_vectors", v, ldv, c, qptr[lo:hi + 1], rptr[lo:hi + 1], hi - lo, int(max_query_cloud), k, idx,
                  tmat, out, ldo)
     return out
@@ -150,49 +104,28 @@ def interpolate_vectors_backward(g, rptr, tptr, tedge, tmat, k, max_ref_cloud, n
     starts at the call's first query row; ``edge_base``: see ``dc_knn_interpolate_backward``.  One launch per 65 535 pairs."""
     from .._lib import lib
     fn = "interpolate_vectors_backward"
-    g, c, ldg = _values(fn, "g", g)
+    g, c, ldg = _cross.values(fn, "g", g, per_point=2)
     k = int(k)
     if not 1 <= k <= MAX_K:
         raise ValueError(f"{fn}: k = {k} outside [1, {MAX_K}]")
     tmat = _table(fn, tmat)
-    rptr = _offsets_of(fn, g.device, rptr=rptr)
+    rptr = _cross.offsets(fn, g.device, rptr=rptr)
     for name, t in (("tptr", tptr), ("tedge", tedge)):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise RuntimeError(f"{fn}: {name} must be a tensor on a HIP device (there is no CPU path)")
+        _cross.device(fn, name, t)
         if t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous():
             raise ValueError(f"{fn}: {name} must be contiguous int64 (knn_cross_transpose)")
     n_ref = int(tptr.numel()) - 1 if n_ref is None else int(n_ref)
-    out, ldo = _out(fn, out, 2 * n_ref, c, g.device)
+    out, ldo = _cross.out_rows(fn, out, 2 * n_ref, c, g.device, on_device=True)
     b = int(rptr.numel()) - 1
     if n_ref == 0:
         return out
     rows = int(g.shape[0]) // 2
     if rows == 0:                              # no query row at all: every edge is skipped, rows that are never read stand in
         g, ldg = g.new_zeros((2, c)), c
-    for lo, hi in _launches(b):
+    for lo, hi in _cross.launches(b):
         lib.call("dc_knn_interpolate_vectors_backward", g, ldg, rows, c, rptr[lo:hi + 1], hi - lo, int(max_ref_cloud), k, tptr,
                  tedge, int(tedge.numel()), int(edge_base), tmat, int(tmat.shape[0]), out, ldo)
     return out
-
-
-class _InterpolateVectors(torch.autograd.Function):
-    """``interpolate_vectors`` on the autograd graph: the forward is the inference kernel (the same bits), the backward ONE launch
-    on transposed lists built beforehand.  ``covered``: every row of v lies in a pair, so the backward writes all of dv itself."""
-
-    @staticmethod
-    def forward(ctx, v, qptr, rptr, idx, tmat, tptr, tedge, mq, mr, n_query, edge_base, covered):
-        ctx.save_for_backward(rptr, tptr, tedge, tmat)
-        ctx.meta = (tuple(v.shape), v.dtype, int(idx.shape[1]), int(mr), int(edge_base), bool(covered))
-        return interpolate_vectors(v.detach(), qptr, rptr, idx, tmat, mq, n_query=n_query)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        rptr, tptr, tedge, tmat = ctx.saved_tensors
-        shape, dtype, k, mr, edge_base, covered = ctx.meta
-        out = torch.empty(shape, dtype=torch.float32, device=g.device) if covered else None
-        dv = interpolate_vectors_backward(g, rptr, tptr, tedge, tmat, k, mr, n_ref=shape[0] // 2, edge_base=edge_base, out=out)
-        return (dv.to(dtype),) + (None,) * 11
 
 
 def knn_interpolate_vectors(v, pos_x, pos_y, frames_x, frames_y, batch_x=None, batch_y=None, k=3, ptr_x=None, ptr_y=None,
@@ -217,20 +150,20 @@ def knn_interpolate_vectors(v, pos_x, pos_y, frames_x, frames_y, batch_x=None, b
     if needs_grad and not differentiable:
         raise RuntimeError(f"{fn}: v requires grad, but the device interpolation is inference-only by default; call it under "
                            "torch.no_grad(), pass v.detach() or differentiable=True")
-    if not torch.is_tensor(v) or not v.is_cuda:
-        raise RuntimeError(f"{fn}: v must be a tensor on a HIP device (there is no CPU path)")
-    _no_grad_inputs(fn, pos_x=pos_x, pos_y=pos_y)
-    pos_x, pos_y = _device_f32(f"{fn}: pos_x", pos_x, 3), _device_f32(f"{fn}: pos_y", pos_y, 3)
+    _cross.device(fn, "v", v)
+    _cross.no_grad_inputs(fn, pos_x=pos_x, pos_y=pos_y)
+    pos_x, pos_y = _cross.rows3(fn, "pos_x", pos_x), _cross.rows3(fn, "pos_y", pos_y)
     if v.dim() != 2 or v.shape[0] != 2 * pos_x.shape[0]:
         raise ValueError(f"{fn}: v must hold two rows per point of pos_x, got {tuple(v.shape)} for {pos_x.shape[0]} points")
     with torch.no_grad():
-        qptr, rptr, b, mq = _pairs(pos_y, pos_x, ptr_y, ptr_x, batch_y, batch_x, fn, max_query_cloud)
+        qptr, rptr, b, mq = _cross.pairs(pos_y, pos_x, ptr_y, ptr_x, batch_y, batch_x, fn, max_query_cloud)
         idx, d2 = knn_cross(pos_y, pos_x, k, ptr_query=qptr, ptr_ref=rptr, max_query_cloud=mq)
     tmat = knn_cross_transport(idx, d2, qptr, rptr, frames_y, frames_x, non_oriented, max_query_cloud=mq)
     with torch.no_grad():
         if not needs_grad:
             return interpolate_vectors(v.detach(), qptr, rptr, idx, tmat, mq, n_query=pos_y.shape[0])
-        mr = int(max_ref_cloud) if max_ref_cloud is not None else (int((rptr[1:] - rptr[:-1]).max()) if b else 0)
+        mr = _cross.largest_cloud(rptr, max_ref_cloud)
         tptr, tedge, _ = knn_cross_transpose(idx, d2, qptr, rptr, num_ref=pos_x.shape[0])
     # offsets given by the caller may leave rows of v outside every cloud: their gradient is zero, filled by the backward
-    return _InterpolateVectors.apply(v, qptr, rptr, idx, tmat, tptr, tedge, mq, mr, pos_y.shape[0], 0, ptr_x is None)
+    return _cross.Interpolate.apply(v, interpolate_vectors, interpolate_vectors_backward, 2, qptr, rptr, idx, tmat, tptr, tedge, tmat,
+                                    mq, mr, pos_y.shape[0], 0, ptr_x is None)

@@ -31,8 +31,9 @@ into the target point's frame by parallel transport before they are weighted (``
 import numpy as np
 import torch
 
-from .geometry.interpolate import MAX_K, _InterpolateRows, interpolate_rows, knn_cross, knn_cross_transpose
-from .geometry.vector_interpolate import _InterpolateVectors, interpolate_vectors, knn_cross_transport
+from .geometry._cross import Interpolate
+from .geometry.interpolate import MAX_K, interpolate_rows, interpolate_rows_backward, knn_cross, knn_cross_transpose
+from .geometry.vector_interpolate import interpolate_vectors, interpolate_vectors_backward, knn_cross_transport
 
 __all__ = ["Propagator", "target_view"]
 
@@ -166,29 +167,37 @@ class Propagator:
                                           (int(self.soff[c0]), int(self.soff[c1])))
         return r
 
+    def _apply(self, what, per, rows_text, fwd, bwd, weights, values, clouds, out):
+        """The body of ``apply`` (per = 1 row per point) and ``apply_vectors`` (per = 2): ``weights(t0, t1)`` gives what `fwd` and
+        `bwd` weight the target rows [t0, t1) of the store with."""
+        clouds = (0, len(self)) if clouds is None else clouds
+        c0, c1 = int(clouds[0]), int(clouds[1])
+        q, s, _, (t0, t1), (s0, s1) = self.cloud_range((c0, c1))
+        if values.dim() != 2 or values.shape[0] != per * (s1 - s0):
+            raise ValueError(f"Propagator.{what}: values must hold {rows_text} {s1 - s0} source rows of clouds {(c0, c1)}, got "
+                             f"{tuple(values.shape)}")
+        mq = int(self.tsizes[c0:c1].max()) if c1 > c0 else 0
+        w_fwd, w_bwd = weights(t0, t1)
+        if self.differentiable and values.requires_grad and torch.is_grad_enabled():
+            if out is not None:
+                raise ValueError(f"Propagator.{what}: out= cannot receive a result that is recorded by autograd")
+            mr = int(self.ssizes[c0:c1].max()) if c1 > c0 else 0
+            tptr, tedge, _ = self.lists
+            # the store-wide lists name target rows of the STORE: the range's first row is subtracted (edge_base; edge e of the
+            # store is entry e - t0 * k of a slice of the table); every source row of the range lies in one of its clouds, so the
+            # backward writes the whole gradient
+            return Interpolate.apply(values, fwd, bwd, per, q, s, self.idx[t0:t1], w_fwd, tptr[s0:s1 + 1], tedge, w_bwd, mq, mr,
+                                     t1 - t0, t0, True)
+        with torch.no_grad():
+            return fwd(values, q, s, self.idx[t0:t1], w_fwd, mq, n_query=t1 - t0, out=out)
+
     def apply(self, values, clouds=None, out=None):
         """values: DEVICE fp32 ``[source rows of the clouds, C]`` (rows may be strided), the clouds ``(c0, c1)`` a contiguous range
         of the set (default: all) -> fp32 ``[target rows of those clouds, C]``.  One launch; no synchronise.  On a
         ``differentiable`` propagator a ``values`` that requires grad (grad mode on) gives a result on the autograd graph -- the
         same forward bits; ``out`` cannot be combined with that.  Otherwise nothing is recorded."""
-        clouds = (0, len(self)) if clouds is None else clouds
-        c0, c1 = int(clouds[0]), int(clouds[1])
-        q, s, _, (t0, t1), (s0, s1) = self.cloud_range((c0, c1))
-        if values.dim() != 2 or values.shape[0] != s1 - s0:
-            raise ValueError(f"Propagator.apply: values must hold the {s1 - s0} source rows of clouds {(c0, c1)}, got "
-                             f"{tuple(values.shape)}")
-        mq = int(self.tsizes[c0:c1].max()) if c1 > c0 else 0
-        if self.differentiable and values.requires_grad and torch.is_grad_enabled():
-            if out is not None:
-                raise ValueError("Propagator.apply: out= cannot receive a result that is recorded by autograd")
-            mr = int(self.ssizes[c0:c1].max()) if c1 > c0 else 0
-            tptr, tedge, tcoef = self.lists
-            # the store-wide lists name target rows of the STORE: the range's first row is subtracted (edge_base); every source
-            # row of the range lies in one of its clouds, so the backward writes the whole gradient
-            return _InterpolateRows.apply(values, q, s, self.idx[t0:t1], self.d2[t0:t1], tptr[s0:s1 + 1], tedge, tcoef, mq, mr,
-                                          t1 - t0, t0, True)
-        with torch.no_grad():
-            return interpolate_rows(values, q, s, self.idx[t0:t1], self.d2[t0:t1], mq, n_query=t1 - t0, out=out)
+        return self._apply("apply", 1, "the", interpolate_rows, interpolate_rows_backward,
+                           lambda t0, t1: (self.d2[t0:t1], self.lists[2] if self.lists else None), values, clouds, out)
 
     def apply_vectors(self, values, clouds=None, out=None):
         """Tangent-vector features: values DEVICE fp32 ``[2 x source rows of the clouds, C]`` (rows 2i, 2i+1 = the coefficients at
@@ -198,23 +207,8 @@ class Propagator:
         backward one launch over the store-wide lists; ``out`` cannot be combined with that."""
         if self.tmat is None:
             raise RuntimeError("Propagator.apply_vectors: this propagator was built without frames= (no transport table)")
-        clouds = (0, len(self)) if clouds is None else clouds
-        c0, c1 = int(clouds[0]), int(clouds[1])
-        q, s, _, (t0, t1), (s0, s1) = self.cloud_range((c0, c1))
-        if values.dim() != 2 or values.shape[0] != 2 * (s1 - s0):
-            raise ValueError(f"Propagator.apply_vectors: values must hold two rows for each of the {s1 - s0} source rows of clouds "
-                             f"{(c0, c1)}, got {tuple(values.shape)}")
-        mq = int(self.tsizes[c0:c1].max()) if c1 > c0 else 0
-        tmat = self.tmat[t0 * self.k:t1 * self.k]
-        if self.differentiable and values.requires_grad and torch.is_grad_enabled():
-            if out is not None:
-                raise ValueError("Propagator.apply_vectors: out= cannot receive a result that is recorded by autograd")
-            mr = int(self.ssizes[c0:c1].max()) if c1 > c0 else 0
-            tptr, tedge, _ = self.lists
-            # store-wide lists, the range's slice of the table: edge e of the store is entry e - t0 * k of the slice (edge_base)
-            return _InterpolateVectors.apply(values, q, s, self.idx[t0:t1], tmat, tptr[s0:s1 + 1], tedge, mq, mr, t1 - t0, t0, True)
-        with torch.no_grad():
-            return interpolate_vectors(values, q, s, self.idx[t0:t1], tmat, mq, n_query=t1 - t0, out=out)
+        return self._apply("apply_vectors", 2, "two rows for each of the", interpolate_vectors, interpolate_vectors_backward,
+                           lambda t0, t1: (self.tmat[t0 * self.k:t1 * self.k],) * 2, values, clouds, out)
 
     @torch.no_grad()
     def labels(self, pred, clouds=None):

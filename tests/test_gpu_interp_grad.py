@@ -125,7 +125,7 @@ def test_gradient_equals_the_restatement_bitwise(k):
                      tptr, tedge, tcoef, int(tedge.numel()), 0, out, ldo)
         torch.cuda.synchronize()
 
-    for c in G.CHANNELS:
+    for c in G.CHANNELS + (1021,):                                              # 1021: 256 groups, one row a workgroup (rpb = 1)
         want = restated_dx(k, c)
         for vec in (True, False):
             g, ldg = laid_out(G.ragged_gradient(c), vec)

@@ -17,7 +17,7 @@ from tests import vector_interp_restate as V
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 GUARD = 8
-CHANNELS = (1, 3, 4, 5, 64)
+CHANNELS = (1, 3, 4, 5, 64, 1021)                                               # 1021: 256 groups, the last of one channel (rpb = 1)
 _cache = {}
 
 
