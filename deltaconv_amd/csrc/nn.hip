@@ -43,6 +43,29 @@ struct BnBwdF {  // dz, dz*xhat
         }
     }
 };
+// the same two addends for the split (synchronised) form, whose parameter gradients and means are sums over MANY ranks' rows:
+// xhat = (h - mean) * invstd in fp64 with mean / invstd taken from the fp64 forward record [sum x | sum x^2 | rows] of the
+// global batch -- the fp32-rounded mean of the coefficient rows costs |mean| invstd 2^-24 per addend, which the cancellation
+// in h - mean turns into tens of ulps of dgamma for columns whose mean is many standard deviations (tests/test_gpu_sync_bn.py).
+// (The per-column quotient and square root do not depend on the row: loop-invariant in colreduce_body.)
+template <int V>
+struct BnBwdF64 {  // dz, dz*xhat
+    const float *dy, *h, *scale, *shift; const double* fwd; long lddy, ldh; float slope, eps; int C;
+    __device__ void operator()(long r, int c0, double (&t)[2][V]) const {
+        const FV<V> g = ldv<V>(dy + r * lddy + c0), x = ldv<V>(h + r * ldh + c0);
+        const double cnt = fwd[2 * C];
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const double mu = fwd[c0 + j] / cnt;
+            double var = fwd[C + c0 + j] / cnt - mu * mu;
+            if (var < 0) var = 0;
+            const double is = 1.0 / sqrt(var + (double)eps);
+            const float z = fmaf(scale[c0 + j], x.v[j], shift[c0 + j]);
+            const float dz = g.v[j] * dcnn::dact(z, slope);
+            t[0][j] = dz; t[1][j] = (double)dz * (((double)x.v[j] - mu) * is);
+        }
+    }
+};
 // vector block: "row" = point i; input rows 2i, 2i+1 of pq.  combine 1: [P | Q] blocked (2*co columns);
 // combine 2: P and Q interleaved (column 2c = P_c, 2c+1 = Q_c) -- what `v_cat @ W.view(2co, K)^T` produces
 // from the reference's [co, 2K] weight without re-stacking it.
@@ -773,21 +796,22 @@ DC_EXPORT int dc_bn_coeffs_from_sums(const double* sums, int64_t count, int32_t 
     return DC_OK;
 }
 
-// backward, step 1: sums[2C] = (sum dz, sum dz * xhat) over this rank's rows
+// backward, step 1: sums[2C] = (sum dz, sum dz * xhat) over this rank's rows; xhat from the all-reduced FORWARD record
+// forward_sums = [sum x (C) | sum x^2 (C) | rows] of the global batch (fp64 mean and invstd: BnBwdF64 above)
 DC_EXPORT int dc_bn_act_backward_sums(const float* dy, int64_t lddy, const float* h, int64_t ldh, int64_t R, int32_t C,
-                                      const float* scale, const float* shift, const float* mean, const float* invstd,
+                                      const float* scale, const float* shift, const double* forward_sums, float eps,
                                       float slope, double* sums, void* workspace, size_t workspace_bytes,
                                       void* stream) {
-    DC_REQUIRE(dy && h && scale && shift && mean && invstd && sums, "dc_bn_act_backward_sums: null pointer");
+    DC_REQUIRE(dy && h && scale && shift && forward_sums && sums, "dc_bn_act_backward_sums: null pointer");
     DC_REQUIRE(R >= 1 && C >= 1 && lddy >= C && ldh >= C, "dc_bn_act_backward_sums: bad size");
     DC_WS_CHECK("dc_bn_act_backward_sums", R, C)
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Ws w = carve(workspace, R, C);
     const SumsFin fin{sums, C, (double)R};
     if (C % 4 == 0 && lddy % 4 == 0 && ldh % 4 == 0 && al16(dy) && al16(h))
-        run_colreduce<4>(BnBwdF<4>{dy, h, scale, shift, mean, invstd, (long)lddy, (long)ldh, slope}, R, C, w, s, fin);
+        run_colreduce<4>(BnBwdF64<4>{dy, h, scale, shift, forward_sums, (long)lddy, (long)ldh, slope, eps, C}, R, C, w, s, fin);
     else
-        run_colreduce<1>(BnBwdF<1>{dy, h, scale, shift, mean, invstd, (long)lddy, (long)ldh, slope}, R, C, w, s, fin);
+        run_colreduce<1>(BnBwdF64<1>{dy, h, scale, shift, forward_sums, (long)lddy, (long)ldh, slope, eps, C}, R, C, w, s, fin);
     DC_CHECK_LAUNCH("dc_bn_act_backward_sums");
     return DC_OK;
 }

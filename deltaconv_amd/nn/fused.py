@@ -68,12 +68,20 @@ def sync_group():
 class BatchStats(int):
     """The `use_batch_stats` flag of a block (truthy, int() == 1) that also remembers the data-parallel group its FORWARD
     statistics were reduced over: the backward pass reduces over the same group whatever `dp.set_sync_bn` says by then
-    (advisor, round 5: a toggle between forward and backward gave global statistics forward and local means backward)."""
+    (advisor, round 5: a toggle between forward and backward gave global statistics forward and local means backward).
+    With a group it also carries `fwd` = (the all-reduced forward record [sum x | sum x^2 | rows], eps): the backward sums form
+    xhat from its fp64 mean (csrc/nn.hip: BnBwdF64)."""
 
-    def __new__(cls, group):
+    def __new__(cls, group, fwd=None):
         self = int.__new__(cls, 1)
-        self.group = group
+        self.group, self.fwd = group, fwd
         return self
+
+
+def _fwd_record(fwd):
+    if fwd is None:
+        raise RuntimeError("synchronised BatchNorm backward needs the all-reduced forward record of its block (fused.BatchStats.fwd)")
+    return fwd
 
 
 def group_of(use):
@@ -134,9 +142,10 @@ def check_bn_rows(bn, rows):
         if group is not None:
             # synchronised statistics span the GLOBAL batch: a rank may hold a single row (one cloud per rank in the
             # categorical head of the segmentation net, deltaconv_amd/dp.py); the all-reduced count is on the device,
-            # so only the case that is decidable without a host sync is refused here
+            # so only the cases that are decidable without a host sync are refused here: one rank in all, and a rank
+            # WITHOUT rows (the kernels want R >= 1; a global batch of one row leaves every other rank in this case)
             import torch.distributed as dist
-            if dist.get_world_size(group) > 1:
+            if dist.get_world_size(group) > 1 and int(rows) == 1:
                 return
         raise ValueError(f"Expected more than 1 value per channel when training, got input size [1, "
                          f"{bn.num_features}, {int(rows)}]")
@@ -176,18 +185,19 @@ def _dgamma_dbeta(c, dev, has_g, has_b):
             torch.empty(c, dtype=torch.float32, device=dev) if has_b else None)
 
 
-def bn_act_backward(dy, lddy, h, coef, gamma, slope, batch_stats, group, has_g=True, has_b=True):
+def bn_act_backward(dy, lddy, h, coef, gamma, slope, batch_stats, group, has_g=True, has_b=True, fwd=None):
     """-> (dh, dgamma, dbeta) of y = leaky_slope(batch_norm(h)) on h [R, C] for the incoming dy (row stride lddy).
     group: the data-parallel group the FORWARD statistics were reduced over, or None -- synchronised statistics take this
-    rank's sums -> all-reduce -> the apply pass with the global means."""
+    rank's sums -> all-reduce -> the apply pass with the global means; fwd = (all-reduced forward record, eps) of the block."""
     r, c = h.shape
     dev = h.device
     dh = torch.empty_like(h)
     dgamma, dbeta = _dgamma_dbeta(c, dev, has_g, has_b)
     ws, nb = _ws(r, c, dev)
     if group is not None:
-        stats, _ = _sync_stats(("dc_bn_act_backward_sums", lambda out: (dy, lddy, h, c, r, c, coef[2], coef[3], coef[0],
-                                                                     coef[1], slope, out, ws, nb)), c, r, dev, group)
+        rec, eps = _fwd_record(fwd)
+        stats, _ = _sync_stats(("dc_bn_act_backward_sums", lambda out: (dy, lddy, h, c, r, c, coef[2], coef[3], rec, eps, slope,
+                                                                     out, ws, nb)), c, r, dev, group)
         m = torch.empty(2, c, dtype=torch.float32, device=dev)
         lib.call("dc_sync_means", stats, c, m[0], m[1], dgamma, dbeta)      # global means + this rank's dgamma / dbeta
         lib.call("dc_bn_act_backward_apply", dy, lddy, h, c, r, c, coef[2], coef[3], coef[0], coef[1], gamma, slope,
@@ -237,6 +247,7 @@ class _BNAct(torch.autograd.Function):
             stats, _ = _sync_stats(("dc_bn_sums", lambda out: (h, r, c, c, out, ws, nb)), c, r, dev, ctx.group)
             lib.call("dc_bn_coeffs_from_sums", stats, 0, c, gamma, beta, eps, momentum, rm, rv, coef[0], coef[1],
                      coef[2], coef[3])
+            ctx.fwd = (stats, eps)
         elif use_batch_stats:
             ws, nb = _ws(r, c, dev)
             lib.call("dc_bn_stats", h, r, c, c, gamma, beta, eps, momentum, rm, rv, coef[0], coef[1], coef[2],
@@ -255,7 +266,8 @@ class _BNAct(torch.autograd.Function):
         h, coef, gamma = ctx.saved_tensors
         training, slope, has_g, has_b, has_res = ctx.cfg
         dy = _c(dy)
-        dh, dgamma, dbeta = bn_act_backward(dy, h.shape[1], h, coef, gamma, slope, training, ctx.group, has_g, has_b)
+        dh, dgamma, dbeta = bn_act_backward(dy, h.shape[1], h, coef, gamma, slope, training, ctx.group, has_g, has_b,
+                                            getattr(ctx, "fwd", None))
         return dh, dgamma, dbeta, None, None, None, None, None, None, (dy if has_res else None)
 
 
@@ -897,7 +909,7 @@ def linear_stats(x, w, bn, gamma, beta, vn=0, defer_final=False):
             lib.call("dc_linear_bn_sums_forward", x, x.stride(0), w, w.stride(0), m, n, k, h, n, sums, 0, ws, nb)
         dp.all_reduce_stats(sums[0], group)
         lib.call("dc_bn_coeffs_from_sums", sums[0], 0, c, gamma, beta, eps, mom, rm, rv, coef[0], coef[1], coef[2], coef[3])
-        return h, coef, BatchStats(group)
+        return h, coef, BatchStats(group, (sums[0], eps))
     if use_batch:
         nb = lib.raw("dc_linear_stats_workspace_bytes")(m, n, k, 0)
         ws = torch.empty((nb + 7) // 8, dtype=torch.float64, device=dev)
@@ -938,8 +950,9 @@ def bn_block_reduce(dy, lddy, inp, h, coef, use_batch, gamma, slope, W, defer_fi
     ws, nb = _ws(r, c, dev)
     coefs = torch.empty(5 * c, dtype=torch.float32, device=dev)
     if group is not None:     # sums of this rank -> all-reduce -> the prologue coefficients from the global sums
-        stats, local = _sync_stats(("dc_bn_act_backward_sums", lambda out: (dy, lddy, h, c, r, c, coef[2], coef[3], coef[0],
-                                                                         coef[1], slope, out, ws, nb)), c, r, dev, group)
+        rec, eps = _fwd_record(getattr(use_batch, "fwd", None))
+        stats, local = _sync_stats(("dc_bn_act_backward_sums", lambda out: (dy, lddy, h, c, r, c, coef[2], coef[3], rec, eps, slope,
+                                                                         out, ws, nb)), c, r, dev, group)
         lib.call("dc_bn_backward_coefs_from_sums", stats, 0, local, c, gamma, coef[2], coef[3], coef[0], coef[1], 1, dg, db,
                  coefs)
     else:

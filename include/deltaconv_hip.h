@@ -488,6 +488,9 @@ int dc_gemm_tn_reduce_many(const int64_t* partials, const int64_t* outs, const i
  *   forward : dc_bn_sums | dc_vn_sums -> all-reduce -> dc_bn_coeffs_from_sums(count = rows of ALL ranks; count <= 0:
  *             the count is on the device at sums[2*C], all-reduced together with the sums -- no host sync)
  *   backward: dc_*_backward_sums -> all-reduce -> m1 = sum_0 / count, m2 = sum_1 / count -> dc_*_backward_apply;
+ *             dc_bn_act_backward_sums takes the all-reduced FORWARD record (forward_sums = [sum x | sum x^2 | rows]) and eps
+ *             instead of the fp32 mean / invstd: xhat = (h - mean) invstd in fp64, so that the cancellation in h - mean
+ *             does not cost dgamma and the second mean |mean| invstd 2^-24 per addend;
  *             dbeta = local sum_0, dgamma = local sum_1 (averaged with the other gradients afterwards). */
 int dc_bn_sums(const float* h, int64_t R, int32_t C, int64_t ldh, double* sums, void* workspace,
                size_t workspace_bytes, void* stream);
@@ -497,7 +500,7 @@ int dc_bn_coeffs_from_sums(const double* sums, int64_t count, int32_t C, const f
                            float eps, float momentum, float* running_mean, float* running_var, float* mean,
                            float* invstd, float* scale, float* shift, void* stream);
 int dc_bn_act_backward_sums(const float* dy, int64_t lddy, const float* h, int64_t ldh, int64_t R, int32_t C,
-                            const float* scale, const float* shift, const float* mean, const float* invstd,
+                            const float* scale, const float* shift, const double* forward_sums, float eps,
                             float slope, double* sums, void* workspace, size_t workspace_bytes, void* stream);
 int dc_sync_means(const double* sums, int32_t C, float* m1, float* m2, float* dgamma, float* dbeta, void* stream);
 int dc_bn_act_backward_apply(const float* dy, int64_t lddy, const float* h, int64_t ldh, int64_t R, int32_t C,
