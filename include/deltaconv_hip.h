@@ -158,7 +158,11 @@ int dc_mls_vector_mapping(const float* pos, const float* normal, const float* x_
                           const float* coords, float* mapping, void* stream);
 
 /* ---- operator applies (SparseTensor @ dense: deltanet_base.py:78; deltaconv.py:57,66;
- *      operators.py:27,33,40,43) ------------------------------------------------------------- */
+ *      operators.py:27,33,40,43) -------------------------------------------------------------
+ * k: the forward entry points below and dc_knn_max / _max_affine / _max_affine_residual / _sum stage (points per block + 1) * k * 12 + 16
+ * bytes of LDS, which must fit 64 KiB: with g = C / V channel groups (V = 4, 2 or 1 floats per access, from C, the leading dimensions and
+ * the base pointers) a block holds 64 points for g <= 4, else ceil(256 / g).  k <= 84 works at every C, g = 5 up to k = 103, g = 8 up to
+ * k = 165, g >= 16 up to k = 255; beyond that the call returns DC_ERR_LAUNCH.  The transposed forms take every k <= 255 at every C. */
 /* out[2Nt,C] = grad @ x[Nt,C] */
 int dc_apply_grad(const float* G, const int32_t* nbr, int32_t n, int32_t k, const float* x, int32_t C, int64_t ldx,
                   float* out, int64_t ldo, void* stream);

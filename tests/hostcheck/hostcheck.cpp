@@ -167,6 +167,11 @@ void hc_ell_fwd(int op, int V, const float* coef, const int* nbr, int n, int k, 
         if (op == 1) HC_FWD(4, div_fwd);
         if (op == 2) HC_FWD(4, divcurlnorm_fwd);
         if (op == 3) HC_FWD(4, hodge_fwd);
+    } else if (V == 2) {    // the 8-byte path (even channel counts / strides / bases: the layer-0 layout)
+        if (op == 0) HC_FWD(2, grad_fwd);
+        if (op == 1) HC_FWD(2, div_fwd);
+        if (op == 2) HC_FWD(2, divcurlnorm_fwd);
+        if (op == 3) HC_FWD(2, hodge_fwd);
     } else {
         if (op == 0) HC_FWD(1, grad_fwd);
         if (op == 1) HC_FWD(1, div_fwd);
@@ -190,6 +195,11 @@ void hc_ell_T(int op, int V, const float* coef, const int* tptr, const int* tedg
         if (op == 1) HC_T(4, (DivT<4>{dy, ldy, dx, ldx, acc, C}));
         if (op == 2) HC_T(4, (DivCurlNormT<4>{dy, ldy, v, ldv, dx, ldx, acc, C}));
         if (op == 3) HC_T(4, (HodgeT<4>{dy, ldy, dx, ldx, acc, C}));
+    } else if (V == 2) {
+        if (op == 0) HC_T(2, (GradT<2>{dy, ldy, dx, ldx, acc, C}));
+        if (op == 1) HC_T(2, (DivT<2>{dy, ldy, dx, ldx, acc, C}));
+        if (op == 2) HC_T(2, (DivCurlNormT<2>{dy, ldy, v, ldv, dx, ldx, acc, C}));
+        if (op == 3) HC_T(2, (HodgeT<2>{dy, ldy, dx, ldx, acc, C}));
     } else {
         if (op == 0) HC_T(1, (GradT<1>{dy, ldy, dx, ldx, acc, C}));
         if (op == 1) HC_T(1, (DivT<1>{dy, ldy, dx, ldx, acc, C}));
@@ -269,6 +279,7 @@ void hc_grad_T_sum(int V, const float* coef, const int* tptr, const int* tedge, 
     for (long j = 0; j < n; ++j)
         for (int c0 = 0; c0 < C; c0 += V) {
             if (V == 4) walk_column(GradTSum<4>{dy, ldy, a, lda, b, ldb, out, ldo, C}, j, c0, coefT.data(), tptr, tedge, k);
+            else if (V == 2) walk_column(GradTSum<2>{dy, ldy, a, lda, b, ldb, out, ldo, C}, j, c0, coefT.data(), tptr, tedge, k);
             else walk_column(GradTSum<1>{dy, ldy, a, lda, b, ldb, out, ldo, C}, j, c0, coefT.data(), tptr, tedge, k);
         }
 }

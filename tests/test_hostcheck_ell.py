@@ -69,7 +69,7 @@ def test_csc(hc, graph):
     assert torch.equal(torch.bincount(flat, minlength=n).to(torch.int32), tptr[1:] - tptr[:-1])
 
 
-@pytest.mark.parametrize("C,pad", [(8, 0), (8, 4), (5, 0), (3, 2), (64, 0)])
+@pytest.mark.parametrize("C,pad", [(8, 0), (8, 4), (5, 0), (3, 2), (64, 0), (6, 0), (8, 2), (64, 6)])
 def test_forward_and_transposed(hc, graph, C, pad):
     """pad > 0 exercises leading dimensions larger than the row (writes into concat buffers)."""
     torch.manual_seed(C)
@@ -77,7 +77,8 @@ def test_forward_and_transposed(hc, graph, C, pad):
     G, D = graph["G"], graph["D"]
     Gc, Dc = G.coef.contiguous(), D.coef.contiguous()
     tptr, tedge = csc(hc, graph)
-    V = 4 if (C % 4 == 0 and pad % 4 == 0) else 1
+    V = 4 if (C % 4 == 0 and pad % 4 == 0) else (2 if (C % 2 == 0 and pad % 2 == 0) else 1)    # pick_v of ell_stage.h
+    VA = 4 if V == 4 else 1                                                                     # the aggregations: 4 or 1
     ld = C + pad
 
     def buf(rows, cols, ldc):
@@ -151,14 +152,14 @@ def test_forward_and_transposed(hc, graph, C, pad):
     hb = torch.zeros(n, ld); hb[:, :C] = h.detach()
     out = buf(n, C, ld)
     arg = torch.zeros(n, C, dtype=torch.uint8)
-    hc.hc_knn_max(V, P(nbr32), n, k, P(hb), C, ld, P(out), ld, P(arg))
+    hc.hc_knn_max(VA, P(nbr32), n, k, P(hb), C, ld, P(out), ld, P(arg))
     ref, ref_arg = h[graph["nbr"]].max(dim=1)
     assert torch.equal(out[:, :C], ref.detach()) and torch.equal(arg.long(), ref_arg)
     dy = torch.randn(n, C)
     (dh_ref,) = torch.autograd.grad(ref, h, dy)
     dyb = torch.zeros(n, ld); dyb[:, :C] = dy
     dh = buf(n, C, ld)
-    hc.hc_knn_max_bwd(V, P(tptr), P(tedge), n, k, P(arg), P(dyb), C, ld, P(dh), ld, 0)
+    hc.hc_knn_max_bwd(VA, P(tptr), P(tedge), n, k, P(arg), P(dyb), C, ld, P(dh), ld, 0)
     assert rel_err(dh[:, :C], dh_ref) < 1e-6
 
     # the same with BatchNorm scale/shift + LeakyReLU folded into the gather (dc_knn_max_affine): dyadic values
@@ -178,7 +179,7 @@ def test_forward_and_transposed(hc, graph, C, pad):
     hb2 = torch.zeros(n, ld); hb2[:, :C] = hq
     out2 = buf(n, C, ld)
     arg2 = torch.zeros(n, C, dtype=torch.uint8)
-    hc.hc_knn_max_affine(V, P(nbr32), n, k, P(hb2), C, ld, P(sc.contiguous()), P(sh.contiguous()), 0.25, P(out2), ld, P(arg2))
+    hc.hc_knn_max_affine(VA, P(nbr32), n, k, P(hb2), C, ld, P(sc.contiguous()), P(sh.contiguous()), 0.25, P(out2), ld, P(arg2))
     assert torch.equal(out2[:, :C], mx) and torch.equal(arg2.long(), slot)
 
     # round 6: the layer's last s_mlp block in the epilogue (dc_knn_max_affine_residual): act2(scale2 h2 + shift2) + max, the same
@@ -188,17 +189,17 @@ def test_forward_and_transposed(hc, graph, C, pad):
     hb3 = torch.zeros(n, ld); hb3[:, :C] = hr
     hb4 = torch.zeros(n, ld); hb4[:, :C] = h2
     mx3, arg3 = buf(n, C, ld), torch.zeros(n, C, dtype=torch.uint8)
-    hc.hc_knn_max_affine(V, P(nbr32), n, k, P(hb3), C, ld, P(s1), P(t1), 0.2, P(mx3), ld, P(arg3))
+    hc.hc_knn_max_affine(VA, P(nbr32), n, k, P(hb3), C, ld, P(s1), P(t1), 0.2, P(mx3), ld, P(arg3))
     z2 = torch.addcmul(t2, s2, h2)                                       # fmaf(scale2, h2, shift2): one rounding
     want = torch.where(z2 > 0, z2, 0.2 * z2) + mx3[:, :C]
     out3, dup3, arg4 = buf(n, C, ld), buf(n, C, ld), torch.zeros(n, C, dtype=torch.uint8)
-    hc.hc_knn_max_affine_residual(V, P(nbr32), n, k, P(hb3), C, ld, P(s1), P(t1), 0.2, P(hb4), ld, P(s2), P(t2),
+    hc.hc_knn_max_affine_residual(VA, P(nbr32), n, k, P(hb3), C, ld, P(s1), P(t1), 0.2, P(hb4), ld, P(s2), P(t2),
                                   0.2, P(out3), ld, P(dup3), ld, P(arg4))
     assert torch.equal(arg4, arg3) and torch.equal(out3[:, :C], dup3[:, :C])
     assert rel_err(out3[:, :C], want) < 2e-7                              # (torch's addcmul may or may not fuse: bits on the GPU test)
 
 
-@pytest.mark.parametrize("C,pad", [(8, 0), (8, 4), (5, 0)])
+@pytest.mark.parametrize("C,pad", [(8, 0), (8, 4), (5, 0), (6, 0), (8, 2)])
 def test_sum_aggregation_and_folded_accumulation(hc, graph, C, pad):
     """dc_knn_sum / dc_knn_sum_backward (DeltaConv(aggr='sum' | 'mean')) and dc_apply_grad_T_sum (transposed gradient
     apply + the other gradients of x') on the CPU build of their per-thread bodies."""
@@ -206,20 +207,21 @@ def test_sum_aggregation_and_folded_accumulation(hc, graph, C, pad):
     n, k, nbr32, G = graph["n"], graph["k"], graph["nbr32"], graph["G"]
     Gc = G.coef.contiguous()
     tptr, tedge = csc(hc, graph)
-    V = 4 if (C % 4 == 0 and pad % 4 == 0) else 1
+    V = 4 if (C % 4 == 0 and pad % 4 == 0) else (2 if (C % 2 == 0 and pad % 2 == 0) else 1)    # pick_v of ell_stage.h
+    VA = 4 if V == 4 else 1                                                                     # the aggregations: 4 or 1
     ld = C + pad
     h = torch.randn(n, C, requires_grad=True)
     hb = torch.zeros(n, ld); hb[:, :C] = h.detach()
     for scale in (1.0, 1.0 / k):
         out = torch.full((n, ld), 7.0)
-        hc.hc_knn_sum(V, P(nbr32), n, k, P(hb), C, ld, scale, P(out), ld)
+        hc.hc_knn_sum(VA, P(nbr32), n, k, P(hb), C, ld, scale, P(out), ld)
         ref = h[graph["nbr"]].sum(1) * scale
         assert rel_err(out[:, :C], ref) < 1e-6 and bool((out[:, C:] == 7).all())
         dy = torch.randn(n, C)
         (dh_ref,) = torch.autograd.grad(ref, h, dy)
         dyb = torch.zeros(n, ld); dyb[:, :C] = dy
         dh = torch.full((n, ld), 7.0)
-        hc.hc_knn_sum_bwd(V, P(tptr), P(tedge), n, k, P(dyb), C, ld, scale, P(dh), ld, 0)
+        hc.hc_knn_sum_bwd(VA, P(tptr), P(tedge), n, k, P(dyb), C, ld, scale, P(dh), ld, 0)
         assert rel_err(dh[:, :C], dh_ref) < 1e-6
     # out = (a + b) + grad^T dy, and with b absent
     x = torch.randn(n, C, requires_grad=True)
