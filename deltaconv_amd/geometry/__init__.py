@@ -9,3 +9,5 @@ from .mesh_normals import vertex_face_lists, vertex_normals_batch    # noqa: F40
 from .interpolate import interpolate_rows_backward, knn_cross, knn_cross_transpose, knn_interpolate  # noqa: F401
 from .connection import *         # noqa: F401,F403
 from .vector_interpolate import *  # noqa: F401,F403
+from .pool import *               # noqa: F401,F403
+from .resample import CloudPair    # noqa: F401

@@ -1,6 +1,6 @@
-"""What the cross-cloud functions share (interpolate.py, vector_interpolate.py, connection.py, propagate.py): their argument
-checks, each written once -- `fn` is the public function the message names, every check returns what the kernels take -- and
-the autograd node of the two interpolations."""
+"""What the cross-cloud functions share (interpolate.py, vector_interpolate.py, pool.py, resample.py, connection.py, propagate.py):
+their argument checks, each written once -- `fn` is the public function the message names, every check returns what the kernels
+take -- and the autograd nodes of the two interpolations and of the pooling."""
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -146,3 +146,26 @@ class Interpolate(torch.autograd.Function):
         out = torch.empty(shape, dtype=torch.float32, device=g.device) if covered else None
         dx = bwd(g, rptr, tptr, tedge, w_bwd, k, mr, n_ref=shape[0] // per, edge_base=edge_base, out=out)
         return (dx.to(dtype),) + (None,) * 15
+
+
+class Pool(torch.autograd.Function):
+    """The cross-cloud pooling on the autograd graph, the sibling of ``Interpolate``: the forward is the inference kernel (the same
+    bits) and keeps what it recorded (``arg``: the slot every maximum / minimum came from, ``cnt``: the valid slots of every query),
+    the backward ONE launch on transposed lists built beforehand.  `fwd` / `bwd`: ``pool_rows`` / ``pool_rows_backward``.
+    ``covered``: every row of x lies in a pair, so the backward writes all of dx itself."""
+
+    @staticmethod
+    def forward(ctx, x, fwd, bwd, reduce, qptr, rptr, idx, tptr, tedge, mq, mr, n_query, covered):
+        out, arg, cnt = fwd(x.detach(), qptr, rptr, idx, mq, reduce, n_query=n_query)
+        ctx.save_for_backward(rptr, tptr, tedge, cnt, *(() if arg is None else (arg,)))
+        ctx.meta = (bwd, reduce, tuple(x.shape), x.dtype, int(idx.shape[1]), int(mr), bool(covered))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        rptr, tptr, tedge, cnt, *arg = ctx.saved_tensors
+        bwd, reduce, shape, dtype, k, mr, covered = ctx.meta
+        out = torch.empty(shape, dtype=torch.float32, device=g.device) if covered else None
+        dx = bwd(g, rptr, tptr, tedge, arg[0] if arg else None, cnt, k, mr, reduce, n_ref=shape[0], out=out)
+        return (dx.to(dtype),) + (None,) * 12

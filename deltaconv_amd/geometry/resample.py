@@ -1,0 +1,165 @@
+"""Both directions between two resolutions of the same clouds in one object: ``CloudPair`` holds the searches, transposed lists and
+transport tables of a fine and a coarse cloud set, each built once, and carries both feature streams across them --
+
+    scalars   down: ``pool_rows`` (max / min / sum / mean over the k_down nearest fine points; csrc/pool.hip)
+              up:   ``interpolate_rows`` (inverse-squared-distance mean of the k_up nearest coarse points; csrc/interp.hip)
+    vectors   down / up: ``interpolate_vectors`` on the respective search and table (parallel transport into the target's frame,
+              then the distance weights; csrc/interp_transport.hip)
+
+-- what a multi-resolution DeltaConv network needs inside a training step (the reference points at it: "GeodesicFPS is used in the
+multiscale architecture", train_shapenet.py:32).  Every backward is an ordered, atomics-free sum: bit-reproducible.  Nothing of the
+geometry is differentiated.  There is no CPU path."""
+import torch
+
+from . import _cross
+from .interpolate import interpolate_rows, interpolate_rows_backward, knn_cross, knn_cross_transpose
+from .pool import _mode, pool_rows, pool_rows_backward
+from .vector_interpolate import interpolate_vectors, interpolate_vectors_backward, knn_cross_transport
+
+__all__ = ["CloudPair"]
+
+
+class CloudPair:
+    """A fine and a coarse set of clouds, cloud b of one belonging to cloud b of the other.
+
+    ``pos_fine [Nf,3]``, ``pos_coarse [Nc,3]``: DEVICE fp32; ``ptr_fine`` / ``ptr_coarse``: int64 ``[B+1]`` ABSOLUTE row offsets.
+    The coarse cloud is the CALLER's -- for instance ``pos_fine[geodesic_fps_batch(...)]`` -- and need not be a subset of the fine
+    one.  ``k_down``: the fine neighbours a coarse point pools over; ``k_up``: the coarse neighbours a fine point interpolates
+    from.  ``frames_fine`` / ``frames_coarse``: ``(normal, x_basis, y_basis)`` over the rows of the respective cloud, as
+    ``build_tangent_basis`` returns them behind the normal; without them the vector methods raise ``ValueError``.
+    ``max_fine_cloud`` / ``max_coarse_cloud``: the largest cloud of each set where the host knows it; with both given nothing
+    here synchronises (otherwise the constructor reads them from the offsets, once).
+
+    Held, each built on first use and once: the down search (coarse queries into fine references, ``k_down``), the up search
+    (fine queries into coarse references, ``k_up``), their transposed lists when ``differentiable`` is set, and the two transport
+    tables when frames are given.  ``prepare()`` builds all of them ahead of a ``torch.cuda.graph`` capture; after it a forward +
+    backward through any composition of the four methods can be captured.
+
+    Every method is on the autograd graph when ``differentiable`` is set and its input requires grad (grad mode on) -- the same
+    forward bits, the backward one launch over the transposed lists; otherwise nothing is recorded and the inference bits are
+    returned.  Positions and frames are never differentiated: one that requires grad raises ``RuntimeError``."""
+
+    def __init__(self, pos_fine, pos_coarse, ptr_fine, ptr_coarse, k_down=16, k_up=3, frames_fine=None, frames_coarse=None,
+                 differentiable=True, max_fine_cloud=None, max_coarse_cloud=None, non_oriented=True):
+        fn = "CloudPair"
+        self.k = {"down": int(k_down), "up": int(k_up)}
+        for name, k in self.k.items():
+            if not 1 <= k <= _cross.MAX_K:
+                raise ValueError(f"{fn}: k_{name} = {k} outside [1, {_cross.MAX_K}]")
+        self.frames = {"fine": self._frames(fn, "frames_fine", frames_fine), "coarse": self._frames(fn, "frames_coarse", frames_coarse)}
+        _cross.no_grad_inputs(fn, pos_fine=pos_fine, pos_coarse=pos_coarse,
+                              **{f"frames_{side}[{i}]": t for side, fr in self.frames.items() if fr for i, t in enumerate(fr)})
+        self.pos = {"fine": _cross.rows3(fn, "pos_fine", pos_fine), "coarse": _cross.rows3(fn, "pos_coarse", pos_coarse)}
+        fptr, cptr = _cross.offsets(fn, self.pos["fine"].device, ptr_fine=ptr_fine, ptr_coarse=ptr_coarse)
+        self.ptr = {"fine": fptr, "coarse": cptr}
+        self.largest = {"fine": _cross.largest_cloud(fptr, max_fine_cloud), "coarse": _cross.largest_cloud(cptr, max_coarse_cloud)}
+        self.differentiable, self.non_oriented = bool(differentiable), bool(non_oriented)
+        self._built = {}
+
+    @staticmethod
+    def _frames(fn, name, frames):
+        if frames is None:
+            return None
+        frames = tuple(frames)
+        if len(frames) != 3 or not all(torch.is_tensor(t) for t in frames):
+            raise ValueError(f"{fn}: {name} = (normal, x_basis, y_basis)")
+        return frames
+
+    # ---- the lazily built pieces; a direction is named by its target: "down" queries coarse -> fine, "up" fine -> coarse ----------
+    @staticmethod
+    def _sides(direction):
+        return ("coarse", "fine") if direction == "down" else ("fine", "coarse")        # (query, reference)
+
+    def _once(self, key, build):
+        if key not in self._built:
+            with torch.no_grad():
+                self._built[key] = build()
+        return self._built[key]
+
+    def search(self, direction):
+        """-> ``(idx int32 [Nq,k], d2 fp32 [Nq,k])`` of the direction's ``knn_cross``."""
+        q, r = self._sides(direction)
+        return self._once(("search", direction), lambda: knn_cross(self.pos[q], self.pos[r], self.k[direction], ptr_query=self.ptr[q],
+                                                                   ptr_ref=self.ptr[r], max_query_cloud=self.largest[q]))
+
+    def lists(self, direction):
+        """-> ``(tptr, tedge, tcoef)`` of the direction's ``knn_cross_transpose``."""
+        q, r = self._sides(direction)
+        return self._once(("lists", direction), lambda: knn_cross_transpose(*self.search(direction), self.ptr[q], self.ptr[r],
+                                                                            num_ref=self.pos[r].shape[0]))
+
+    def table(self, direction):
+        """-> the direction's ``knn_cross_transport`` table; ``ValueError`` without frames."""
+        q, r = self._sides(direction)
+        if self.frames[q] is None or self.frames[r] is None:
+            raise ValueError(f"CloudPair.{direction}_vectors: this pair was built without frames_fine= / frames_coarse= "
+                             "(no transport table)")
+        return self._once(("table", direction), lambda: knn_cross_transport(*self.search(direction), self.ptr[q], self.ptr[r],
+                                                                            self.frames[q], self.frames[r], self.non_oriented,
+                                                                            max_query_cloud=self.largest[q]))
+
+    def prepare(self):
+        """Builds every piece the four methods can need, so that nothing is left to build inside a capture."""
+        for direction in ("down", "up"):
+            self.search(direction)
+            if self.differentiable:
+                self.lists(direction)
+            if self.frames["fine"] is not None and self.frames["coarse"] is not None:
+                self.table(direction)
+        return self
+
+    # ---- the four methods -----------------------------------------------------------------------------------------------------
+    def _recorded(self, t):
+        return self.differentiable and torch.is_tensor(t) and t.requires_grad and torch.is_grad_enabled()
+
+    def _rows(self, what, t, side, per=1):
+        _cross.device(f"CloudPair.{what}", "the input", t)
+        n = self.pos[side].shape[0]
+        if t.dim() != 2 or t.shape[0] != per * n:
+            raise ValueError(f"CloudPair.{what}: the input must hold {'two rows' if per == 2 else 'one row'} per {side} point "
+                             f"([{per * n}, C]), got {tuple(t.shape)}")
+
+    def down(self, x, reduce="max"):
+        """Scalar features ``[Nf,C]`` pooled to the coarse clouds -> ``[Nc,C]``: ``reduce`` over the ``k_down`` nearest fine points
+        (``"max" | "min" | "sum" | "add" | "mean"``, ``knn_pool``)."""
+        _mode("CloudPair.down", reduce)
+        self._rows("down", x, "fine")
+        idx, _ = self.search("down")
+        q, r = self.ptr["coarse"], self.ptr["fine"]
+        mq, n = self.largest["coarse"], self.pos["coarse"].shape[0]
+        if self._recorded(x):
+            tptr, tedge, _ = self.lists("down")
+            return _cross.Pool.apply(x, pool_rows, pool_rows_backward, reduce, q, r, idx, tptr, tedge, mq, self.largest["fine"], n, False)
+        with torch.no_grad():
+            return pool_rows(x.detach(), q, r, idx, mq, reduce, n_query=n)[0]
+
+    def _interpolate(self, direction, per, fwd, bwd, t, w_fwd, w_bwd):
+        qs, rs = self._sides(direction)
+        idx, _ = self.search(direction)
+        q, r = self.ptr[qs], self.ptr[rs]
+        mq, n = self.largest[qs], self.pos[qs].shape[0]
+        if self._recorded(t):
+            tptr, tedge, tcoef = self.lists(direction)
+            return _cross.Interpolate.apply(t, fwd, bwd, per, q, r, idx, w_fwd, tptr, tedge, tcoef if w_bwd is None else w_bwd, mq,
+                                            self.largest[rs], n, 0, False)
+        with torch.no_grad():
+            return fwd(t.detach(), q, r, idx, w_fwd, mq, n_query=n)
+
+    def up(self, x):
+        """Scalar features ``[Nc,C]`` interpolated to the fine clouds -> ``[Nf,C]`` (``knn_interpolate`` over ``k_up``)."""
+        self._rows("up", x, "coarse")
+        return self._interpolate("up", 1, interpolate_rows, interpolate_rows_backward, x, self.search("up")[1], None)
+
+    def down_vectors(self, v):
+        """Tangent-vector features ``[2*Nf,C]`` in the fine frames -> ``[2*Nc,C]`` in the coarse frames: the transported,
+        distance-weighted pooling over ``k_down`` (``knn_interpolate_vectors`` with the coarse cloud as the target)."""
+        tmat = self.table("down")
+        self._rows("down_vectors", v, "fine", 2)
+        return self._interpolate("down", 2, interpolate_vectors, interpolate_vectors_backward, v, tmat, tmat)
+
+    def up_vectors(self, v):
+        """Tangent-vector features ``[2*Nc,C]`` in the coarse frames -> ``[2*Nf,C]`` in the fine frames
+        (``knn_interpolate_vectors`` over ``k_up``)."""
+        tmat = self.table("up")
+        self._rows("up_vectors", v, "coarse", 2)
+        return self._interpolate("up", 2, interpolate_vectors, interpolate_vectors_backward, v, tmat, tmat)

@@ -990,6 +990,45 @@ int dc_knn_interpolate_vectors_backward(const float* g, int64_t ldg, int64_t num
                                         int64_t num_edges, int64_t edge_base, const float* tmat, int64_t tmat_rows, float* dv,
                                         int64_t ldv, void* stream);
 
+/* ---- scalar features from a cloud DOWN to a sampled one: pooling over a two-set search (csrc/pool.hip, csrc/pool_math.h) --------- */
+/* Stands in for a torch_cluster.knn search followed by torch_scatter.scatter(x[col], row, reduce = "max" | "min" | "sum" | "mean"):
+ * the set-abstraction step of PointNet++, on the result of dc_knn_cross with the SAMPLED cloud as the query and the full cloud as
+ * the reference.  It is no call site of the reference, which pools inside one cloud only; it is what its multi-resolution use
+ * (GeodesicFPS, train_shapenet.py:32) needs between two.
+ * out[q,c] = reduce over the valid slots s of x[rptr[b] + idx[q,s], c]  (mode: 0 max, 1 min, 2 sum, 3 mean -- the codes of
+ * dc_seg_reduce), csrc/pool_math.h: a slot with idx outside [0, size of the reference cloud) is skipped and indexes nothing; the
+ * first valid slot is copied bit for bit (k = 1 is an exact gather), a later one replaces it iff it is strictly larger (max) /
+ * smaller (min) -- ties keep the nearer slot, a NaN in a later slot is never taken, one in the first valid slot stays -- or is added,
+ * every addition rounded on its own, slots in order (sum, mean); mean divides once by (float)cnt.  No valid slot: a row of zeros,
+ * arg 255, cnt 0.
+ *   x           DEVICE [*,ldx] fp32 reference rows, C <= ldx; out DEVICE [*,ldo] fp32, C <= ldo
+ *   qptr, rptr, max_query_cloud, k, idx   as in dc_knn_interpolate (the same grid: chunks of 256 queries x cloud pairs)
+ *   arg         DEVICE uint8 [*,ldarg], C <= ldarg: the slot 0 .. k-1 every channel of a max / min came from (one 32-bit store per
+ *               group of 4 channels where arg is 4-byte aligned and ldarg a multiple of 4, byte stores otherwise); not written by
+ *               sum / mean, for which it may be NULL
+ *   cnt         DEVICE uint8 [*]: the number of valid slots of every query row of a pair, written in every mode
+ * 16-byte loads / stores where the base pointer and the leading dimension allow, scalar otherwise: any C >= 1, the same bits.
+ * The argument checks of dc_knn_interpolate, and: mode outside 0 .. 3, ldarg below C, a NULL cnt, a NULL arg for max / min:
+ * DC_ERR_ARG with a message, checked before anything touches the device.  One launch, stream-ordered, no allocation, no
+ * synchronisation, no atomics, capturable. */
+int dc_knn_pool(const float* x, int64_t ldx, int32_t C, const int64_t* qptr, const int64_t* rptr, int32_t B,
+                int64_t max_query_cloud, int32_t k, const int32_t* idx, int32_t mode, float* out, int64_t ldo, uint8_t* arg,
+                int64_t ldarg, uint8_t* cnt, void* stream);
+/* The gradient of dc_knn_pool w.r.t. x -- what autograd records for the gather x[col] is an index_add_ with floating-point atomics --
+ * on the lists of dc_knn_cross_transpose (tptr, tedge; its tcoef is not needed).  For reference row r: dx[r,c] = 0, then for every
+ * in-edge e of r in ascending order, q = e / k, s = e - q * k: max / min add g[q,c] iff arg[q,c] == s (an edge that lost adds
+ * nothing), sum adds g[q,c], mean adds g[q,c] / (float)cnt[q]; quotient and sum each rounded on their own (csrc/pool_math.h).
+ * Every reference row of every pair is written (a row without in-edges gets zeros).
+ *   g           DEVICE [num_g_rows, ldg] fp32, C <= ldg; an edge whose query row falls outside [0, num_g_rows) is skipped
+ *   rptr, max_ref_cloud, tptr, tedge, num_edges   as in dc_knn_interpolate_backward (the same grid)
+ *   arg, ldarg, cnt   what dc_knn_pool wrote, indexed like g; arg may be NULL for sum / mean
+ *   dx          DEVICE [*, ldx] fp32, C <= ldx
+ * The argument checks of dc_knn_interpolate_backward and the mode / arg / cnt checks of dc_knn_pool: DC_ERR_ARG.  One launch, no
+ * atomics, the same bits on every run, capturable. */
+int dc_knn_pool_backward(const float* g, int64_t ldg, int64_t num_g_rows, int32_t C, const int64_t* rptr, int32_t B,
+                         int64_t max_ref_cloud, int32_t k, const int64_t* tptr, const int64_t* tedge, int64_t num_edges,
+                         int32_t mode, const uint8_t* arg, int64_t ldarg, const uint8_t* cnt, float* dx, int64_t ldx, void* stream);
+
 /* ---- per-vertex normals of a store of triangle meshes (csrc/mesh_normal.hip, csrc/mesh_normal_math.h) --------------------------- */
 /* First half of what replaces GenerateMeshNormals() in the reference's ShapeSeg pre_transform (experiments/train_shapeseg.py:31,
  * torch_geometric's transform: an index_add_ of the face normals onto their corners): the vertex-to-incident-corner lists of a whole

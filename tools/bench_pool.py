@@ -1,0 +1,122 @@
+"""Cross-cloud pooling benchmark: scalar features of full clouds pooled down to sampled ones AND the gradient brought back to the
+full rows -- 32 clouds of 8 192 points down to 1 024 each (every 8th point), k = 16, C = 64 and 128, ``reduce="max"``; whole
+forward + backward passes on a finished search, each ending in a device synchronise:
+
+  (a) a torch restatement on the device: the gather ``x[ids]`` (an ``[Nq, k, C]`` intermediate), ``amax(1)``, and autograd's
+      backward of both (an ``index_put_(accumulate=True)`` that may use floating-point atomics: torch gives no run-to-run
+      guarantee for it)
+  (b) ``CloudPair.down(x)`` and its backward: ``dc_knn_pool`` + ``dc_knn_pool_backward`` on the transposed lists built once
+      (ordered sums, no atomics, the same bits every run)
+
+The legs alternate in one process, ``--repeats`` times each after a warm-up pass each; the yardstick is leg (a) of the same run
+and its run-to-run spread.  No speed-up is claimed in advance: the expectation is "(b) no slower than (a) beyond (a)'s spread".
+Needs an MI355X.
+
+    python tools/bench_pool.py --out profiles/device_pool.txt
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from deltaconv_amd.geometry import CloudPair
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--clouds", type=int, default=32)
+    ap.add_argument("--points", type=int, default=8192, help="points of a full cloud")
+    ap.add_argument("--num", type=int, default=1024, help="points of a sampled cloud (every points/num-th point)")
+    ap.add_argument("--channels", type=int, nargs="+", default=[64, 128])
+    ap.add_argument("--k", type=int, default=16)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--out", default=None, help="also write the report to this file")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/bench_pool.py needs an MI355X: neither leg has a CPU form")
+    dev = torch.device("cuda", 0)
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    b, n, m, k = args.clouds, args.points, args.num, args.k
+    gen = torch.Generator().manual_seed(1)
+    pos = torch.rand(b * n, 3, generator=gen).to(dev)
+    coarse = pos.view(b, n, 3)[:, ::n // m][:, :m].reshape(b * m, 3).contiguous()
+    fptr = (torch.arange(b + 1, dtype=torch.int64) * n).to(dev)
+    cptr = (torch.arange(b + 1, dtype=torch.int64) * m).to(dev)
+    pair = CloudPair(pos, coarse, fptr, cptr, k_down=k, max_fine_cloud=n, max_coarse_cloud=m).prepare()
+    idx = pair.search("down")[0]
+    tptr = pair.lists("down")[0]
+    torch.cuda.synchronize(dev)
+    lengths = (tptr[1:] - tptr[:-1]).float()
+    say(f"# cross-cloud pooling benchmark on {torch.cuda.get_device_name(0)}: every time is one whole forward + backward pass on a "
+        f"finished search, wall clock, device synchronise at the end, after one warm-up pass per leg; the legs alternate, "
+        f"{args.repeats} repeats; reduce = max")
+    say(f"## {b} clouds of {n} points down to {m}, k = {k}: {int(tptr[-1])} in-edges, per full-cloud row mean {float(lengths.mean()):.2f}, "
+        f"largest {int(lengths.max())}, rows without one {int((lengths == 0).sum())}")
+    # leg (a): what the search result looks like to torch -- absolute source rows, prepared once (every slot is valid here)
+    assert bool((idx >= 0).all())
+    ids = (fptr[:-1].repeat_interleave(m)[:, None] + idx.long())
+
+    def leg_a(x, grad):
+        out = x[ids].amax(1)
+        out.backward(grad)
+        torch.cuda.synchronize(dev)
+        return out
+
+    def leg_b(x, grad):
+        out = pair.down(x)
+        out.backward(grad)
+        torch.cuda.synchronize(dev)
+        return out
+
+    for c in args.channels:
+        values = torch.randn(b * n, c, generator=gen).to(dev)
+        grad = torch.randn(b * m, c, generator=gen).to(dev)
+        say(f"## C = {c}: algorithmic bytes of a pass {(b * m * (k * (4 * c + 4) + 2 * 4 * c + c + 1) + int(tptr[-1]) * (4 * c + c + 8) + b * n * (4 * c + 8)) / 1e6:.0f} MB "
+            f"(forward: per slot a {4 * c}-byte row of x and a 4-byte id, per sampled row {4 * c} bytes of out, {c} of arg and 1 of cnt; "
+            f"backward: per in-edge a {4 * c}-byte row of g, {c} bytes of arg and an 8-byte edge id, per full row {4 * c} bytes of dx "
+            f"and an 8-byte list offset)")
+        grads, outs = {}, {}
+        for key, fn in (("a", leg_a), ("b", leg_b)):                            # the warm-up passes double as the comparison
+            x = values.clone().requires_grad_(True)
+            outs[key] = fn(x, grad).detach()
+            grads[key] = x.grad
+        same = {}
+        for key, fn in (("a", leg_a), ("b", leg_b)):
+            x = values.clone().requires_grad_(True)
+            fn(x, grad)
+            same[key] = bool(torch.equal(x.grad, grads[key]))
+        say(f"    largest |(b) - (a)|: forward {float((outs['b'] - outs['a']).abs().max()):.3e}, gradient "
+            f"{float((grads['b'] - grads['a']).abs().max()):.3e} (largest |gradient| {float(grads['a'].abs().max()):.3e}); a second "
+            f"run gives the same gradient bits: (a) {'yes' if same['a'] else 'no'}, (b) {'yes' if same['b'] else 'NO'}")
+        del outs, grads
+        times = {"a": [], "b": []}
+        for _ in range(args.repeats):
+            for key, fn in (("a", leg_a), ("b", leg_b)):
+                x = values.clone().requires_grad_(True)
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                fn(x, grad)
+                times[key].append(time.perf_counter() - t0)
+        med = {key: sorted(v)[len(v) // 2] for key, v in times.items()}
+        for key, what in (("a", "torch gather x[ids] + amax(1), autograd's backward"), ("b", "CloudPair.down + ordered backward")):
+            say(f"({key}) {what}: " + ", ".join(f"{t * 1e3:.3f}" for t in times[key]) + f" ms / pass; median {med[key] * 1e3:.3f} ms")
+        spread = max(times["a"]) - min(times["a"])
+        say(f"    spread of (a) over its repeats (max - min): {spread * 1e3:.3f} ms = {spread / med['a'] * 100:.2f} %")
+        say(f"    (a) / (b) = {med['a'] / med['b']:.2f} (medians) -> (b) no slower than (a) beyond (a)'s spread: "
+            f"{'yes' if med['b'] <= med['a'] + spread else 'NO'}")
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
