@@ -425,6 +425,72 @@ void hc_edge(const float* y, const int* nbr, const int* tptr, const int* tedge, 
                           mean.data(), invstd.data(), m1.data(), m2.data(), training, dy, C);
 }
 
+// The same chain with every intermediate returned (tests/edge_restate.py holds each one to its fp64 bound), at V = 4 or 1.
+// The finalisers are restated from colreduce.h: BnFin over R = E rows with the running statistics (updated in place when
+// training), BwdFin (dgamma, dbeta, m1, m2), and bn_eval_coeffs_kernel for the inference map.  coef = [mean | invstd | scale |
+// shift], m12 = [m1 | m2].
+extern "C++" {
+template <int V>
+static void edge_all(const float* y, const int* nbr, const int* tptr, const int* tedge, int n, int k, int C, const float* gamma,
+                     const float* beta, float eps, float momentum, float slope, int training, float* run_mean, float* run_var,
+                     float* amax, float* amin, unsigned char* amx, unsigned char* amn, float* s1, float* coef, float* out,
+                     unsigned char* arg, const float* dout, float* dzs, float* dy, float* dgamma, float* dbeta, float* m12) {
+    using namespace dcedge;
+    float *mean = coef, *invstd = coef + C, *scale = coef + 2 * C, *shift = coef + 3 * C, *m1 = m12, *m2 = m12 + C;
+    std::vector<double> q1(C, 0.0), q2(C, 0.0);
+    for (long i = 0; i < n; ++i)
+        for (int c0 = 0; c0 < C; c0 += V) {
+            double t[2][V];
+            edge_gather<V>(i, c0, y, C, nbr, k, amax, amin, amx, amn, s1, C, C, t);
+            for (int q = 0; q < V; ++q) { q1[c0 + q] += t[0][q]; q2[c0 + q] += t[1][q]; }
+        }
+    const long E = (long)n * k;
+    for (int c = 0; c < C; ++c) {
+        if (training) {
+            const double m = q1[c] / (double)E;
+            double var = q2[c] / (double)E - m * m;
+            if (var < 0) var = 0;
+            const double is = 1.0 / sqrt(var + (double)eps);
+            mean[c] = (float)m; invstd[c] = (float)is;
+            scale[c] = (float)(gamma[c] * is); shift[c] = (float)(beta[c] - m * gamma[c] * is);
+            const double unb = E > 1 ? var * (double)E / (double)(E - 1) : var;
+            run_mean[c] = (float)((1.0 - momentum) * run_mean[c] + momentum * m);
+            run_var[c] = (float)((1.0 - momentum) * run_var[c] + momentum * unb);
+        } else {
+            const float is = 1.f / sqrtf(run_var[c] + eps);
+            mean[c] = run_mean[c]; invstd[c] = is;
+            scale[c] = gamma[c] * is; shift[c] = beta[c] - run_mean[c] * gamma[c] * is;
+        }
+    }
+    for (long i = 0; i < n; ++i)
+        for (int c = 0; c < C; ++c) {
+            out[i * C + c] = dcnn::act(fmaf(scale[c], pick(scale[c], amax[i * C + c], amin[i * C + c]), shift[c]), slope);
+            arg[i * C + c] = scale[c] >= 0.f ? amx[i * C + c] : amn[i * C + c];
+        }
+    std::vector<double> a(C, 0.0), b(C, 0.0);
+    for (long i = 0; i < n; ++i)
+        for (int c = 0; c < C; ++c) {
+            float dz, dza;
+            edge_bwd_terms(dout[i * C + c], amax[i * C + c], amin[i * C + c], scale[c], shift[c], mean[c], invstd[c], slope, dz, dza);
+            dzs[i * C + c] = dz; a[c] += dz; b[c] += dza;
+        }
+    for (int c = 0; c < C; ++c) { dbeta[c] = (float)a[c]; dgamma[c] = (float)b[c]; m1[c] = (float)(a[c] / (double)E); m2[c] = (float)(b[c] / (double)E); }
+    for (long t = 0; t < (long)n * (C / V); ++t)
+        edge_bwd_point<V>(t, C / V, tptr, tedge, k, y, C, dzs, s1, C, amx, amn, C, scale, mean, invstd, m1, m2, training, dy, C);
+}
+}  // extern "C++"
+void hc_edge_all(int V, const float* y, const int* nbr, const int* tptr, const int* tedge, int n, int k, int C, const float* gamma,
+                 const float* beta, float eps, float momentum, float slope, int training, float* run_mean, float* run_var,
+                 float* amax, float* amin, unsigned char* amx, unsigned char* amn, float* s1, float* coef, float* out,
+                 unsigned char* arg, const float* dout, float* dzs, float* dy, float* dgamma, float* dbeta, float* m12) {
+    if (V == 4)
+        edge_all<4>(y, nbr, tptr, tedge, n, k, C, gamma, beta, eps, momentum, slope, training, run_mean, run_var, amax, amin, amx, amn,
+                    s1, coef, out, arg, dout, dzs, dy, dgamma, dbeta, m12);
+    else
+        edge_all<1>(y, nbr, tptr, tedge, n, k, C, gamma, beta, eps, momentum, slope, training, run_mean, run_var, amax, amin, amx, amn,
+                    s1, coef, out, arg, dout, dzs, dy, dgamma, dbeta, m12);
+}
+
 // training loss: mean over rows of ce_row, gradient per row (loss.hip runs the same body per thread)
 double hc_ce_loss(const float* x, const long* label, long R, int C, float eps, float* dx) {
     double s = 0.0;
