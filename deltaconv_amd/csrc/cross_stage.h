@@ -94,12 +94,13 @@ __global__ __launch_bounds__(THREADS) void cross_bwd_kernel(const int64_t* __res
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 // What an apply entry point tells its launcher about itself: its name (the first word of every message), the names of the leading
 // dimension of the rows it reads, of the rows it writes and of their leading dimension, the argument list of its null-pointer
-// message with whether the pointers the launcher does not see are there, and the table its body reads 16 bytes at a time (tmat;
-// null: none).
+// message with whether the pointers the launcher does not see are there, the table its body reads 16 bytes at a time (null: none)
+// and the name of that argument in its entry point's message.
 struct Call {
     const char *fn, *ld_in, *out, *ld_out, *nulls;
     bool others;
     const void* table;
+    const char* table_name = "tmat";
 };
 
 inline int check_shape(const Call& c, int B, int k, int C, long long ld_in, long long ld_out) {
@@ -122,7 +123,7 @@ int launch_fwd(const Call& c, const float* in, long long ld_in, int C, const int
                max_query_cloud);
     if (B == 0 || max_query_cloud == 0) return DC_OK;
     DC_REQUIRE(in && qptr && rptr && c.others && out, "%s: null pointer (%s)", c.fn, c.nulls);
-    DC_REQUIRE(aligned_to(c.table, 16), "%s: tmat must be 16-byte aligned", c.fn);
+    DC_REQUIRE(aligned_to(c.table, 16), "%s: %s must be 16-byte aligned", c.fn, c.table_name);
     hipLaunchKernelGGL((cross_fwd_kernel<BODY>), dim3(dc_cdiv(max_query_cloud, THREADS), B), dim3(THREADS), 0,
                        static_cast<hipStream_t>(stream), qptr, rptr, C, out, ld_out, rows_vec(in, ld_in), rows_vec(out, ld_out), body);
     DC_CHECK_LAUNCH(c.fn);
@@ -143,7 +144,7 @@ int launch_bwd(const Call& c, const float* g, long long ld_in, long long num_g_r
     DC_REQUIRE(rptr && tptr && dx, "%s: null pointer (rptr, tptr, %s)", c.fn, c.out);
     const bool readable = g && c.others;
     DC_REQUIRE(empty || num_edges == 0 || num_g_rows == 0 || readable, "%s: null pointer (%s)", c.fn, c.nulls);
-    DC_REQUIRE(aligned_to(c.table, 16), "%s: tmat must be 16-byte aligned", c.fn);
+    DC_REQUIRE(aligned_to(c.table, 16), "%s: %s must be 16-byte aligned", c.fn, c.table_name);
     if (!readable) num_edges = 0;
     const int groups = (C + 3) >> 2, rpb = groups >= THREADS ? 1 : THREADS / groups;
     hipLaunchKernelGGL((cross_bwd_kernel<BODY>), dim3(dc_cdiv(max_ref_cloud, rpb), B), dim3(THREADS), 0,

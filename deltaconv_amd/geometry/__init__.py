@@ -10,4 +10,5 @@ from .interpolate import interpolate_rows_backward, knn_cross, knn_cross_transpo
 from .connection import *         # noqa: F401,F403
 from .vector_interpolate import *  # noqa: F401,F403
 from .pool import *               # noqa: F401,F403
-from .resample import CloudPair    # noqa: F401
+from .pool_vectors import *       # noqa: F401,F403
+from .resample import CloudPair, prefix_levels    # noqa: F401

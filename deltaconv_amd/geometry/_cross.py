@@ -1,6 +1,6 @@
-"""What the cross-cloud functions share (interpolate.py, vector_interpolate.py, pool.py, resample.py, connection.py, propagate.py):
-their argument checks, each written once -- `fn` is the public function the message names, every check returns what the kernels
-take -- and the autograd nodes of the two interpolations and of the pooling."""
+"""What the cross-cloud functions share (interpolate.py, vector_interpolate.py, pool.py, pool_vectors.py, resample.py,
+connection.py, propagate.py): their argument checks, each written once -- `fn` is the public function the message names, every
+check returns what the kernels take -- and the autograd nodes of the two interpolations and of the two poolings."""
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -169,3 +169,24 @@ class Pool(torch.autograd.Function):
         out = torch.empty(shape, dtype=torch.float32, device=g.device) if covered else None
         dx = bwd(g, rptr, tptr, tedge, arg[0] if arg else None, cnt, k, mr, reduce, n_ref=shape[0], out=out)
         return (dx.to(dtype),) + (None,) * 12
+
+
+class PoolVectors(torch.autograd.Function):
+    """``Pool`` for tangent-vector features (two rows per point): `fwd` / `bwd`: ``pool_vectors`` / ``pool_vectors_backward``,
+    ``rmat`` the rotation table of the search, read by both."""
+
+    @staticmethod
+    def forward(ctx, v, fwd, bwd, reduce, qptr, rptr, idx, rmat, tptr, tedge, mq, mr, n_query, covered):
+        out, arg, cnt = fwd(v.detach(), qptr, rptr, idx, rmat, mq, reduce, n_query=n_query)
+        ctx.save_for_backward(rptr, tptr, tedge, rmat, cnt, *(() if arg is None else (arg,)))
+        ctx.meta = (bwd, reduce, tuple(v.shape), v.dtype, int(idx.shape[1]), int(mr), bool(covered))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        rptr, tptr, tedge, rmat, cnt, *arg = ctx.saved_tensors
+        bwd, reduce, shape, dtype, k, mr, covered = ctx.meta
+        out = torch.empty(shape, dtype=torch.float32, device=g.device) if covered else None
+        dv = bwd(g, rptr, tptr, tedge, rmat, arg[0] if arg else None, cnt, k, mr, reduce, n_ref=shape[0] // 2, out=out)
+        return (dv.to(dtype),) + (None,) * 13

@@ -5,6 +5,8 @@ transport tables of a fine and a coarse cloud set, each built once, and carries 
               up:   ``interpolate_rows`` (inverse-squared-distance mean of the k_up nearest coarse points; csrc/interp.hip)
     vectors   down / up: ``interpolate_vectors`` on the respective search and table (parallel transport into the target's frame,
               then the distance weights; csrc/interp_transport.hip)
+              down, pooled: ``pool_vectors`` on the down search and its rotation table (parallel transport, then the vector of
+              largest norm / the mean / the sum over the k_down nearest fine points; csrc/pool_vectors.hip)
 
 -- what a multi-resolution DeltaConv network needs inside a training step (the reference points at it: "GeodesicFPS is used in the
 multiscale architecture", train_shapenet.py:32).  Every backward is an ordered, atomics-free sum: bit-reproducible.  Nothing of the
@@ -13,10 +15,12 @@ import torch
 
 from . import _cross
 from .interpolate import interpolate_rows, interpolate_rows_backward, knn_cross, knn_cross_transpose
+from .graph import PtrInfo
 from .pool import _mode, pool_rows, pool_rows_backward
+from .pool_vectors import knn_cross_rotation, pool_vectors, pool_vectors_backward
 from .vector_interpolate import interpolate_vectors, interpolate_vectors_backward, knn_cross_transport
 
-__all__ = ["CloudPair"]
+__all__ = ["CloudPair", "prefix_levels"]
 
 
 class CloudPair:
@@ -33,7 +37,8 @@ class CloudPair:
     Held, each built on first use and once: the down search (coarse queries into fine references, ``k_down``), the up search
     (fine queries into coarse references, ``k_up``), their transposed lists when ``differentiable`` is set, and the two transport
     tables when frames are given.  ``prepare()`` builds all of them ahead of a ``torch.cuda.graph`` capture; after it a forward +
-    backward through any composition of the four methods can be captured.
+    backward through any composition of the four methods can be captured.  The down ROTATION table, which only
+    ``down_vectors(v, reduce="max" | "mean" | "sum")`` reads, is built on its first use, or by ``prepare(vector_pool=True)``.
 
     Every method is on the autograd graph when ``differentiable`` is set and its input requires grad (grad mode on) -- the same
     forward bits, the backward one launch over the transposed lists; otherwise nothing is recorded and the inference bits are
@@ -98,14 +103,28 @@ class CloudPair:
                                                                             self.frames[q], self.frames[r], self.non_oriented,
                                                                             max_query_cloud=self.largest[q]))
 
-    def prepare(self):
-        """Builds every piece the four methods can need, so that nothing is left to build inside a capture."""
+    def rotation(self, direction):
+        """-> the direction's ``knn_cross_rotation`` table (the transport matrices alone, what ``down_vectors(v, reduce=...)``
+        pools through); ``ValueError`` without frames."""
+        q, r = self._sides(direction)
+        if self.frames[q] is None or self.frames[r] is None:
+            raise ValueError(f"CloudPair.{direction}_vectors: this pair was built without frames_fine= / frames_coarse= "
+                             "(no rotation table)")
+        return self._once(("rotation", direction), lambda: knn_cross_rotation(self.search(direction)[0], self.ptr[q], self.ptr[r],
+                                                                              self.frames[q], self.frames[r], self.non_oriented,
+                                                                              max_query_cloud=self.largest[q]))
+
+    def prepare(self, vector_pool=False):
+        """Builds every piece the four methods can need, so that nothing is left to build inside a capture.  ``vector_pool``:
+        also the down rotation table, which only ``down_vectors(v, reduce="max" | "mean" | "sum")`` reads."""
         for direction in ("down", "up"):
             self.search(direction)
             if self.differentiable:
                 self.lists(direction)
             if self.frames["fine"] is not None and self.frames["coarse"] is not None:
                 self.table(direction)
+        if vector_pool:
+            self.rotation("down")
         return self
 
     # ---- the four methods -----------------------------------------------------------------------------------------------------
@@ -150,12 +169,36 @@ class CloudPair:
         self._rows("up", x, "coarse")
         return self._interpolate("up", 1, interpolate_rows, interpolate_rows_backward, x, self.search("up")[1], None)
 
-    def down_vectors(self, v):
-        """Tangent-vector features ``[2*Nf,C]`` in the fine frames -> ``[2*Nc,C]`` in the coarse frames: the transported,
-        distance-weighted pooling over ``k_down`` (``knn_interpolate_vectors`` with the coarse cloud as the target)."""
-        tmat = self.table("down")
+    def down_vectors(self, v, reduce="interpolate"):
+        """Tangent-vector features ``[2*Nf,C]`` in the fine frames -> ``[2*Nc,C]`` in the coarse frames, over the ``k_down``
+        nearest fine points of every coarse point, each carried into the coarse point's frame by parallel transport.
+
+        ``reduce="interpolate"`` (the default): the distance-weighted mean of ``knn_interpolate_vectors`` with the coarse cloud
+        as the target.  On a coarse cloud that is a SUBSET of the fine one -- every cloud ``geodesic_fps_batch``,
+        ``geodesic_subsample`` and ``T.GeodesicFPS`` produce -- it DEGENERATES: the coincident fine point has ``d^2 = 0``, weight
+        ``1e16`` and coefficient exactly 1.0 in fp32, the other neighbours about 1e-13, so the result is the gather of the coarse
+        points' own vectors and the other ``k_down - 1`` neighbours contribute nothing.  It is a correct interpolation.
+
+        ``reduce="max" | "mean" | "sum" | "add"``: the pooling of ``knn_pool_vectors`` (csrc/pool_vectors.hip) -- per channel the
+        transported vector of largest norm, or the unweighted mean / sum.  Its rotation table is built on first use and once
+        (``rotation("down")``; ahead of a capture: ``prepare(vector_pool=True)``)."""
+        if reduce == "interpolate":
+            tmat = self.table("down")
+            self._rows("down_vectors", v, "fine", 2)
+            return self._interpolate("down", 2, interpolate_vectors, interpolate_vectors_backward, v, tmat, tmat)
+        if reduce not in ("max", "mean", "sum", "add"):
+            raise ValueError(f"CloudPair.down_vectors: reduce must be one of 'interpolate', 'max', 'mean', 'sum', 'add', got {reduce!r}")
+        rmat = self.rotation("down")
         self._rows("down_vectors", v, "fine", 2)
-        return self._interpolate("down", 2, interpolate_vectors, interpolate_vectors_backward, v, tmat, tmat)
+        idx, _ = self.search("down")
+        q, r = self.ptr["coarse"], self.ptr["fine"]
+        mq, n = self.largest["coarse"], self.pos["coarse"].shape[0]
+        if self._recorded(v):
+            tptr, tedge, _ = self.lists("down")
+            return _cross.PoolVectors.apply(v, pool_vectors, pool_vectors_backward, reduce, q, r, idx, rmat, tptr, tedge, mq,
+                                            self.largest["fine"], n, False)
+        with torch.no_grad():
+            return pool_vectors(v.detach(), q, r, idx, rmat, mq, reduce, n_query=n)[0]
 
     def up_vectors(self, v):
         """Tangent-vector features ``[2*Nc,C]`` in the coarse frames -> ``[2*Nf,C]`` in the fine frames
@@ -163,3 +206,45 @@ class CloudPair:
         tmat = self.table("up")
         self._rows("up_vectors", v, "coarse", 2)
         return self._interpolate("up", 2, interpolate_vectors, interpolate_vectors_backward, v, tmat, tmat)
+
+
+def prefix_levels(ptr_info, ratios):
+    """The levels of a multi-resolution network whose coarser clouds are PREFIXES of the finer ones: level ``l + 1`` keeps the
+    first ``ceil(n_b / ratios[l])`` rows of every cloud b of level l.  -> a list of ``(rows, ptr, info)``, one per level, level 0
+    first: ``rows`` int64 ``[N_l]`` on the device, the level's rows as row ids into LEVEL 0 (None at level 0: every row); ``ptr``
+    int64 ``[B+1]`` the level's row offsets (what ``CloudPair`` takes); ``info`` a ``PtrInfo`` (int32 offsets, B, largest cloud)
+    whose ``min_cloud`` is set -- largest and smallest cloud are derived on the host, ``ceil`` is monotone.
+
+    The hierarchy is a farthest-point-sampling hierarchy EXACTLY WHEN the rows of every cloud are in FPS pick order: FPS is greedy,
+    so the first m picks of an n-point sample are the m-point sample from the same start (tests/test_fps_prefix_host.py).
+    ``geodesic_subsample`` (the dataset recipes) writes its rows in pick order, and so puts them there; on clouds in any other
+    order the prefixes are still valid levels, but arbitrary subsets.
+
+    ``ptr_info``: the ``PtrInfo`` of level 0 (``(ptr, B, largest cloud)`` with ``min_cloud``; a plain tuple or a missing
+    ``min_cloud`` costs one read of the offsets).  A UNIFORM batch (largest == smallest cloud: what ``DeviceLoader`` feeds a
+    captured step) synchronises nothing: level l has ``B * n_l`` rows.  A ragged batch reads its coarse total once per level."""
+    from .graph import _min_cloud
+    ptr0, b, mx = ptr_info[0], int(ptr_info[1]), int(ptr_info[2])
+    mn = _min_cloud(ptr_info)
+    ratios = [int(r) for r in ratios]
+    if any(r < 1 for r in ratios):
+        raise ValueError(f"prefix_levels: ratios must be integers >= 1, got {ratios}")
+    dev = ptr0.device
+    levels = [(None, ptr0.to(torch.int64), PtrInfo(ptr0.to(torch.int32), b, mx, mn))]
+    uniform = mx == mn
+    sizes = None if uniform else (ptr0[1:] - ptr0[:-1]).to(torch.int64)
+    cloud = torch.arange(b, dtype=torch.int64, device=dev)
+    for r in ratios:
+        mx, mn = -(-mx // r), -(-mn // r)
+        if uniform:
+            ptr = torch.arange(b + 1, dtype=torch.int64, device=dev) * mx
+            rows = (levels[0][1][:-1, None] + torch.arange(mx, dtype=torch.int64, device=dev)[None, :]).reshape(-1)
+        else:
+            sizes = (sizes + (r - 1)) // r
+            ptr = torch.zeros(b + 1, dtype=torch.int64, device=dev)
+            ptr[1:] = torch.cumsum(sizes, 0)
+            total = int(ptr[-1])                       # the one host read of the level
+            of = torch.repeat_interleave(cloud, sizes, output_size=total)
+            rows = torch.arange(total, dtype=torch.int64, device=dev) - ptr[of] + levels[0][1][of]
+        levels.append((rows, ptr, PtrInfo(ptr.to(torch.int32), b, mx, mn)))
+    return levels

@@ -11,11 +11,17 @@ from ..nn.layer import cat_outputs
 
 class DeltaNetSegmentation(torch.nn.Module):
     def __init__(self, in_channels, num_classes, conv_channels=[64, 128, 256], mlp_depth=2, embedding_size=1024,
-                 categorical_vector=False, num_neighbors=20, grad_regularizer=0.001, grad_kernel_width=1):
+                 categorical_vector=False, num_neighbors=20, grad_regularizer=0.001, grad_kernel_width=1, *, backbone=None):
+        """backbone (beyond the reference signature): a module whose forward returns the list of per-point features and whose
+        ``out_widths`` lists their channel counts; it stands in for the DeltaNetBase that is built otherwise
+        (DeltaNetMultiscaleSegmentation brings its own)."""
         super().__init__()
         self.categorical_vector = categorical_vector
-        self.deltanet_base = DeltaNetBase(in_channels, conv_channels, mlp_depth, num_neighbors, grad_regularizer,
-                                          grad_kernel_width)
+        if backbone is None:
+            backbone = DeltaNetBase(in_channels, conv_channels, mlp_depth, num_neighbors, grad_regularizer, grad_kernel_width)
+        else:
+            conv_channels = list(backbone.out_widths)
+        self.deltanet_base = backbone
         self.lin_global = MLP([sum(conv_channels), embedding_size])
         extra = 0
         if categorical_vector:

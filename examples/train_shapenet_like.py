@@ -20,14 +20,19 @@ import torch.distributed as dist
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import deltaconv_amd as deltaconv                       # the drop-in: was `import deltaconv`
-from deltaconv_amd.models import DeltaNetSegmentation
+from deltaconv_amd.models import DeltaNetMultiscaleSegmentation, DeltaNetSegmentation
 from deltaconv_amd.utils import calc_loss, calc_shape_IoU
 from deltaconv_amd.dp import FlatGradDataParallel
 from deltaconv_amd.data import synthetic_batch
 
 
 def shapenet_model(args, num_classes):
-    """train_shapenet.py:76-89."""
+    """train_shapenet.py:76-89; --multiscale: the multi-resolution network over prefix levels (rows in FPS pick order, as
+    geodesic_subsample writes them, make the levels an FPS hierarchy)."""
+    if getattr(args, "multiscale", False):
+        return DeltaNetMultiscaleSegmentation(in_channels=3, num_classes=num_classes, mlp_depth=2, embedding_size=1024,
+                                              num_neighbors=args.k, grad_regularizer=args.grad_regularizer,
+                                              grad_kernel_width=args.grad_kernel, categorical_vector=True)
     return DeltaNetSegmentation(in_channels=3, num_classes=num_classes, conv_channels=[64, 128, 256], mlp_depth=2,
                                 embedding_size=1024, num_neighbors=args.k, grad_regularizer=args.grad_regularizer,
                                 grad_kernel_width=args.grad_kernel, categorical_vector=True)
@@ -120,6 +125,8 @@ def main(argv=None):
     ap.add_argument("--train_batches", type=int, default=4)
     ap.add_argument("--logdir", default="runs/shapenet_like")
     ap.add_argument("--data", default=None, help="ShapeNet part root (raw/<synset>/*.txt, raw/train_test_split/*.json)")
+    ap.add_argument("--multiscale", action="store_true",
+                    help="DeltaNetMultiscaleSegmentation: three levels (ratios 4, 4) with transported max-pooling of the vector stream")
     ap.add_argument("--device-loader", action="store_true",
                     help="with --data: keep the prepared dataset on the GPU, build and augment every batch in one launch "
                          "(deltaconv_amd.DeviceLoader) instead of per-shape transforms + collate + upload on the host")

@@ -1029,6 +1029,60 @@ int dc_knn_pool_backward(const float* g, int64_t ldg, int64_t num_g_rows, int32_
                          int64_t max_ref_cloud, int32_t k, const int64_t* tptr, const int64_t* tedge, int64_t num_edges,
                          int32_t mode, const uint8_t* arg, int64_t ldarg, const uint8_t* cnt, float* dx, int64_t ldx, void* stream);
 
+/* ---- tangent-vector features from a cloud DOWN to a sampled one: transported pooling (csrc/pool_vectors.hip, csrc/pool_vectors_math.h) */
+/* The rotation table of a dc_knn_cross result: entry e = q * k + s (q the ABSOLUTE query row, the row of idx) is
+ * R = the connection of dc_build_transport from the source frame (sn, sx)[rptr[b] + idx[e]] into the target frame (tn, tx, ty)[q] --
+ * the matrix alone, WITHOUT the interpolation coefficient dc_knn_cross_transport multiplies in (it takes no d2).  A slot with idx
+ * outside [0, size of the reference cloud) holds four +0.0f and indexes nothing.
+ *   qptr, rptr, num_query, max_query_cloud, k, idx, tn, tx, ty, sn, sx, non_oriented   as in dc_knn_cross_transport (the same grid)
+ *   rmat        DEVICE [num_query * k, 4] fp32, 16-byte aligned; rows of queries outside every pair are not written
+ * The argument checks of dc_knn_cross_transport: DC_ERR_ARG with a message, checked before anything touches the device.  One launch,
+ * one thread and one 16-byte store per slot, stream-ordered, no allocation, no synchronisation, no atomics, capturable. */
+int dc_knn_cross_rotation(const int64_t* qptr, const int64_t* rptr, int32_t B, int64_t num_query, int64_t max_query_cloud, int32_t k,
+                          const int32_t* idx, const float* tn, const float* tx, const float* ty, const float* sn, const float* sx,
+                          int32_t non_oriented, float* rmat, void* stream);
+/* The set-abstraction step of dc_knn_pool for the vector stream, on the result of dc_knn_cross with the SAMPLED cloud as the query
+ * and on the table of dc_knn_cross_rotation: every neighbour's vector is carried into the query's frame, then reduced.  It is no call
+ * site of the reference.  Vector rows as in dc_transport_sum: rows 2i, 2i+1 are the two coefficients at point i.  For query row q of
+ * pair b, valid slots s = 0 .. k-1 in order (idx outside the reference cloud: skipped), j = rptr[b] + idx[q,s], v0 = v[2j,c],
+ * v1 = v[2j+1,c], R = rmat[q*k + s]  (mode: 0 max, 2 sum, 3 mean -- the codes of dc_seg_reduce; 1, min, is refused):
+ *   sum    au = av = +0, au = (au + R00*v0) + R01*v1, av = (av + R10*v0) + R11*v1: dc_knn_interpolate_vectors on rmat, bit for bit
+ *   mean   the sum, then one division per component by (float)cnt
+ *   max    per channel the slot of the largest key v0*v0 + v1*v1 (taken in the source frame): the first valid slot, a later one iff
+ *          its key is strictly larger -- ties keep the nearer slot, a NaN key in a later slot is never taken, one in the first valid
+ *          slot stays; out = (R00*v0 + R01*v1, R10*v0 + R11*v1) of that slot, arg = the slot
+ * every product, sum and quotient rounded to fp32 on its own (csrc/pool_vectors_math.h); out[2q,c] = au, out[2q+1,c] = av.  No valid
+ * slot: zeros, arg 255, cnt 0.
+ *   v           DEVICE [*,ldv] fp32, two rows per reference point, C <= ldv; out DEVICE [*,ldo] fp32, two rows per query, C <= ldo
+ *   qptr, rptr, max_query_cloud, k, idx   as in dc_knn_interpolate (the same grid); rmat 16-byte aligned, indexed like idx
+ *   arg         DEVICE uint8 [*,ldarg], one row per QUERY, C <= ldarg: the slot every channel of a max came from (one 32-bit store
+ *               per group of 4 channels where arg is 4-byte aligned and ldarg a multiple of 4, byte stores otherwise); not written by
+ *               sum / mean, for which it may be NULL
+ *   cnt         DEVICE uint8 [*]: the number of valid slots of every query row of a pair, written in every mode
+ * 16-byte loads / stores where the base pointer and the leading dimension allow, scalar otherwise: any C >= 1, the same bits.
+ * The argument checks of dc_knn_interpolate, and: mode outside {0, 2, 3}, ldarg below C, a NULL cnt, a NULL arg for max, a
+ * misaligned rmat: DC_ERR_ARG with a message, checked before anything touches the device.  One launch, stream-ordered, no
+ * allocation, no synchronisation, no atomics, capturable. */
+int dc_knn_pool_vectors(const float* v, int64_t ldv, int32_t C, const int64_t* qptr, const int64_t* rptr, int32_t B,
+                        int64_t max_query_cloud, int32_t k, const int32_t* idx, const float* rmat, int32_t mode, float* out,
+                        int64_t ldo, uint8_t* arg, int64_t ldarg, uint8_t* cnt, void* stream);
+/* The gradient of dc_knn_pool_vectors w.r.t. v on the lists of dc_knn_cross_transpose (tptr, tedge; its tcoef is not read).  For
+ * reference row r: du = dw = +0, then for every in-edge e of r in ascending order, q = e / k, s = e - q * k, R = rmat[e],
+ * g0 = g[2q,c], g1 = g[2q+1,c]: du = (du + R00*g0) + R10*g1, dw = (dw + R01*g0) + R11*g1 -- for every edge (sum), with g0, g1 first
+ * divided by (float)cnt[q], each quotient rounded on its own (mean), or iff arg[q,c] == s (max: an edge that lost adds nothing);
+ * dv[2r,c] = du, dv[2r+1,c] = dw.  Every reference row of every pair is written (a row without in-edges gets zeros).
+ *   g           DEVICE [2 * num_g_rows, ldg] fp32, C <= ldg; an edge whose query row falls outside [0, num_g_rows) is skipped
+ *   rptr, max_ref_cloud, tptr, tedge, num_edges   as in dc_knn_interpolate_backward (the same grid)
+ *   rmat        DEVICE [num_g_rows * k, 4] fp32, 16-byte aligned, indexed like the rows of g
+ *   arg, ldarg, cnt   what dc_knn_pool_vectors wrote, one row per query of g; arg may be NULL for sum / mean
+ *   dv          DEVICE [*, ldv] fp32, two rows per reference point, C <= ldv
+ * The argument checks of dc_knn_interpolate_backward, the mode / arg / cnt checks of dc_knn_pool_vectors and a misaligned rmat:
+ * DC_ERR_ARG.  One launch, no atomics, the same bits on every run, capturable. */
+int dc_knn_pool_vectors_backward(const float* g, int64_t ldg, int64_t num_g_rows, int32_t C, const int64_t* rptr, int32_t B,
+                                 int64_t max_ref_cloud, int32_t k, const int64_t* tptr, const int64_t* tedge, int64_t num_edges,
+                                 const float* rmat, int32_t mode, const uint8_t* arg, int64_t ldarg, const uint8_t* cnt, float* dv,
+                                 int64_t ldv, void* stream);
+
 /* ---- per-vertex normals of a store of triangle meshes (csrc/mesh_normal.hip, csrc/mesh_normal_math.h) --------------------------- */
 /* First half of what replaces GenerateMeshNormals() in the reference's ShapeSeg pre_transform (experiments/train_shapeseg.py:31,
  * torch_geometric's transform: an index_add_ of the face normals onto their corners): the vertex-to-incident-corner lists of a whole
