@@ -498,3 +498,319 @@ double hc_ce_loss(const float* x, const long* label, long R, int C, float eps, f
     return s / (double)R;
 }
 }
+
+// ---- the single-rank entry points of nn.hip with the kernels' own chunk and lane order (tests/nn_restate.py holds every
+// output to its fp64 bound; tests/test_nn_restate_host.py).  colreduce.h and nn.hip cannot be included on the host (device
+// intrinsics, launches), so their loops are restated here next to the lines they mirror; every element formula comes from
+// nn_math.h.  The vector width V of a kernel only decides which thread owns a column, never the arithmetic of an element or
+// the order of a column's sum, so the loops below run per column.
+namespace hcnn {
+using namespace dcnn;
+constexpr int RT = 16, CT = 16;                                              // colreduce.h:13-14
+static long cdivl(long a, long b) { return (a + b - 1) / b; }
+static int rows_per_chunk(long R, int C, int blocks = 768) {                 // colreduce.h:270-274
+    const long coltiles = (C + CT * 4 - 1) / (CT * 4);
+    long rpc = (R * coltiles / blocks + RT - 1) / RT * RT;
+    return (int)std::min<long>(std::max<long>(rpc, RT), 512);
+}
+static int tile_rows(long R, int C, int V) {                                 // nn.hip: run_tile
+    const long coltiles = cdivl(C, CT * V);
+    long rpc = (R * coltiles / 1024 + RT - 1) / RT * RT;
+    return (int)std::min<long>(std::max<long>(rpc, RT), 1024);
+}
+// colreduce.h:32-73 (colreduce_body) and :96-109 (colreduce_final_kernel): per chunk the 16 row lanes walk r0 + rl, + RT, ...
+// in fp64, the lanes are added in order, the chunks are strided over 64 finaliser lanes and joined by the xor butterfly of
+// dc_wave_sum (common.h).  mk(chunk, lane, column) makes the functor of one thread: a stateful one (PoolBwdF) starts fresh there.
+template <class MK>
+static void colreduce(MK mk, long R, int C, std::vector<double>& s0, std::vector<double>& s1) {
+    const int rpc = rows_per_chunk(R, C), chunks = (int)cdivl(R, rpc);
+    s0.assign(C, 0.0); s1.assign(C, 0.0);
+    std::vector<double> p0(chunks), p1(chunks);
+    for (int c = 0; c < C; ++c) {
+        for (int ch = 0; ch < chunks; ++ch) {
+            const long r0 = (long)ch * rpc, r1 = std::min<long>(r0 + rpc, R);
+            double a0 = 0, a1 = 0;
+            for (int rl = 0; rl < RT; ++rl) {
+                auto f = mk(ch, rl, c);
+                double l0 = 0, l1 = 0;
+                for (long r = r0 + rl; r < r1; r += RT) { double t0, t1; f(r, c, t0, t1); l0 += t0; l1 += t1; }
+                a0 += l0; a1 += l1;
+            }
+            p0[ch] = a0; p1[ch] = a1;
+        }
+        double w0[64], w1[64];
+        for (int l = 0; l < 64; ++l) {
+            double t0 = 0, t1 = 0;
+            for (int ch = l; ch < chunks; ch += 64) { t0 += p0[ch]; t1 += p1[ch]; }
+            w0[l] = t0; w1[l] = t1;
+        }
+        for (int o = 32; o > 0; o >>= 1)
+            for (int l = 0; l < o; ++l) { w0[l] += w0[l ^ o]; w1[l] += w1[l ^ o]; }      // lane 0's value of the butterfly
+        s0[c] = w0[0]; s1[c] = w1[0];
+    }
+}
+// colreduce.h:112-131 (BnFin)
+static void bn_fin(long R, int C, const std::vector<double>& s0, const std::vector<double>& s1, const float* gamma, const float* beta,
+                   float eps, float momentum, float* rm, float* rv, float* mean, float* invstd, float* scale, float* shift) {
+    for (int c = 0; c < C; ++c) {
+        const double m = s0[c] / (double)R;
+        double var = s1[c] / (double)R - m * m;
+        if (var < 0) var = 0;
+        const double is = 1.0 / sqrt(var + (double)eps);
+        const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
+        mean[c] = (float)m; invstd[c] = (float)is; scale[c] = (float)(g * is); shift[c] = (float)(b - m * g * is);
+        if (rm) {
+            const double unb = R > 1 ? var * (double)R / (double)(R - 1) : var;
+            rm[c] = (float)((1.0 - momentum) * rm[c] + momentum * m);
+            rv[c] = (float)((1.0 - momentum) * rv[c] + momentum * unb);
+        }
+    }
+}
+// nn.hip:75-99 (vn_load_y) for one column
+static void vn_load(const float* in, long ld, long i, int c, int co, int combine, float& yu, float& yv) {
+    const float *ru = in + (2 * i) * ld, *rv = in + (2 * i + 1) * ld;
+    if (combine == 2) vn_combine(ru[2 * c], ru[2 * c + 1], rv[2 * c], rv[2 * c + 1], yu, yv);
+    else if (combine) vn_combine(ru[c], ru[co + c], rv[c], rv[co + c], yu, yv);
+    else { yu = ru[c]; yv = rv[c]; }
+}
+// nn.hip:328-349 (PoolDy): the per-cloud values cached by one thread, reloaded when its row enters another cloud
+struct PoolDy {
+    const float* dp; const int* argmax; long ldp; int N, C, with_mean;
+    int cur_b = -1; float dmx = 0, dme = 0; int ar = 0;
+    float get(long r, int c) {
+        const int b = (int)((unsigned)r / (unsigned)N);
+        if (b != cur_b) {
+            cur_b = b;
+            dmx = dp[(long)b * ldp + c];
+            dme = with_mean ? dp[(long)b * ldp + C + c] / (float)N : 0.f;
+            ar = argmax[(long)b * C + c];
+        }
+        const int row = (int)r - b * N;
+        return (ar == row ? dmx : 0.f) + dme;
+    }
+};
+// the tile kernel's walk (nn.hip:131-144): thread (row chunk, lane) of a column takes rows r0 + rl, + RT, ...
+template <class BODY>
+static void tile_walk(long R, int C, int V, BODY body) {
+    const int rpc = tile_rows(R, C, V);
+    for (int c = 0; c < C; ++c)
+        for (long r0 = 0; r0 < R; r0 += rpc)
+            for (int rl = 0; rl < RT; ++rl) {
+                auto th = body(c);
+                for (long r = r0 + rl; r < std::min<long>(r0 + rpc, R); r += RT) th(r);
+            }
+}
+}  // namespace hcnn
+
+extern "C" {
+void hc_nn_bn_stats(const float* h, long R, int C, const float* gamma, const float* beta, float eps, float momentum, float* rm,
+                    float* rv, float* mean, float* invstd, float* scale, float* shift) {
+    std::vector<double> s0, s1;
+    hcnn::colreduce([&](int, int, int) {                                      // nn.hip:25-32 (StatsF)
+        return [&](long r, int c, double& t0, double& t1) { const float x = h[r * C + c]; t0 = (double)x; t1 = (double)x * (double)x; };
+    }, R, C, s0, s1);
+    hcnn::bn_fin(R, C, s0, s1, gamma, beta, eps, momentum, rm, rv, mean, invstd, scale, shift);
+}
+void hc_nn_vn_stats(const float* in, long n, int co, int combine, const float* gamma, const float* beta, float eps, float momentum,
+                    float* rm, float* rv, float* mean, float* invstd, float* scale, float* shift) {
+    const long ld = combine ? 2 * co : co;
+    std::vector<double> s0, s1;
+    hcnn::colreduce([&](int, int, int) {                                      // nn.hip:100-109 (VnStatsF)
+        return [&](long i, int c, double& t0, double& t1) {
+            float yu, yv;
+            hcnn::vn_load(in, ld, i, c, co, combine, yu, yv);
+            const double nn = dcnn::vn_norm(yu, yv);
+            t0 = nn; t1 = nn * nn;
+        };
+    }, n, co, s0, s1);
+    hcnn::bn_fin(n, co, s0, s1, gamma, beta, eps, momentum, rm, rv, mean, invstd, scale, shift);
+}
+// colreduce.h:249-259 (bn_eval_coeffs_kernel)
+void hc_nn_eval_coeffs(const float* gamma, const float* beta, const float* rm, const float* rv, float eps, int C, float* mean,
+                       float* invstd, float* scale, float* shift) {
+    for (int c = 0; c < C; ++c) {
+        const float is = 1.f / sqrtf(rv[c] + eps);
+        const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
+        mean[c] = rm[c]; invstd[c] = is; scale[c] = g * is; shift[c] = b - rm[c] * g * is;
+    }
+}
+// nn.hip:146-168 (BnActBody)
+void hc_nn_bn_act(const float* h, long R, int C, const float* scale, const float* shift, float slope, const float* res, float* y,
+                  float* y2) {
+    hcnn::tile_walk(R, C, 4, [&](int c) {
+        return [&, c](long r) {
+            float o = dcnn::act(fmaf(scale[c], h[r * C + c], shift[c]), slope);
+            if (res) o += res[r * C + c];
+            y[r * C + c] = o;
+            if (y2) y2[r * C + c] = o;
+        };
+    });
+}
+// nn.hip:33-45 (BnBwdF) into colreduce.h:145-164 (BwdCoefFin); coefs [5, C]
+void hc_nn_bwd_reduce(const float* dy, const float* h, long R, int C, const float* scale, const float* shift, const float* mean,
+                      const float* invstd, const float* gamma, float slope, int training, float* dgamma, float* dbeta, float* coefs) {
+    std::vector<double> s0, s1;
+    hcnn::colreduce([&](int, int, int) {
+        return [&](long r, int c, double& t0, double& t1) {
+            float a, b;
+            dcnn::bn_bwd_terms(dy[r * C + c], h[r * C + c], scale[c], shift[c], mean[c], invstd[c], slope, a, b);
+            t0 = a; t1 = b;
+        };
+    }, R, C, s0, s1);
+    for (int c = 0; c < C; ++c) {
+        if (dbeta) dbeta[c] = (float)s0[c];
+        if (dgamma) dgamma[c] = (float)s1[c];
+        const double gi = (double)(gamma ? gamma[c] : 1.f) * (double)invstd[c];
+        coefs[c] = scale[c];
+        coefs[C + c] = shift[c];
+        if (training) {
+            const double m1 = s0[c] / (double)R, m2 = s1[c] / (double)R, is = invstd[c], mu = mean[c];
+            coefs[2 * C + c] = (float)gi;
+            coefs[3 * C + c] = (float)(-gi * m2 * is);
+            coefs[4 * C + c] = (float)(-gi * m1 + gi * m2 * is * mu);
+        } else {
+            coefs[2 * C + c] = scale[c]; coefs[3 * C + c] = 0.f; coefs[4 * C + c] = 0.f;
+        }
+    }
+}
+// dc_bn_act_backward (pool == 0: BnBwdF, BnActBwdBody) and dc_bn_act_pool_backward (pool != 0: PoolBwdF, PoolBwdBody with the
+// gradient rebuilt by PoolDy in each thread's own row order) into colreduce.h:133-141 (BwdFin)
+void hc_nn_bwd(int pool, const float* dy, const float* dp, const int* argmax, int N, int with_mean, const float* h, long R, int C,
+               const float* scale, const float* shift, const float* mean, const float* invstd, const float* gamma, float slope,
+               int training, float* dh, float* dgamma, float* dbeta) {
+    const long ldp = with_mean ? 2 * C : C;
+    std::vector<double> s0, s1;
+    hcnn::colreduce([&](int, int, int) {
+        return [&, cache = hcnn::PoolDy{dp, argmax, ldp, N, C, with_mean}](long r, int c, double& t0, double& t1) mutable {
+            const float g = pool ? cache.get(r, c) : dy[r * C + c];
+            float a, b;
+            dcnn::bn_bwd_terms(g, h[r * C + c], scale[c], shift[c], mean[c], invstd[c], slope, a, b);
+            t0 = a; t1 = b;
+        };
+    }, R, C, s0, s1);
+    std::vector<float> m1(C), m2(C);
+    for (int c = 0; c < C; ++c) {
+        if (dbeta) dbeta[c] = (float)s0[c];
+        if (dgamma) dgamma[c] = (float)s1[c];
+        m1[c] = (float)(s0[c] / (double)R); m2[c] = (float)(s1[c] / (double)R);
+    }
+    for (int V : {4, 1}) {                       // both widths' row chunks: the cache is reloaded at other rows, the bits are the same
+        std::vector<float> out((size_t)R * C);
+        hcnn::tile_walk(R, C, V, [&](int c) {
+            return [&, c, cache = hcnn::PoolDy{dp, argmax, ldp, N, C, with_mean}](long r) mutable {
+                const float g = pool ? cache.get(r, c) : dy[r * C + c];
+                out[r * C + c] = dcnn::bn_bwd_dh(g, h[r * C + c], scale[c], shift[c], mean[c], invstd[c], slope,
+                                                 (gamma ? gamma[c] : 1.f) * invstd[c], m1[c], m2[c], training);
+            };
+        });
+        if (V == 4) memcpy(dh, out.data(), out.size() * sizeof(float));
+        else if (memcmp(dh, out.data(), out.size() * sizeof(float)) != 0) dh[0] = NAN;       // the two walks must agree
+    }
+}
+// nn.hip:193-213 (VnApplyBody)
+void hc_nn_vn_apply(const float* in, long n, int co, int combine, const float* scale, const float* shift, float* out) {
+    const long ld = combine ? 2 * co : co;
+    hcnn::tile_walk(n, co, 4, [&](int c) {
+        return [&, c](long i) {
+            float yu, yv;
+            hcnn::vn_load(in, ld, i, c, co, combine, yu, yv);
+            const float s = dcnn::vn_scale(dcnn::vn_norm(yu, yv), scale[c], shift[c]);
+            out[(2 * i) * co + c] = yu * s;
+            out[(2 * i + 1) * co + c] = yv * s;
+        };
+    });
+}
+// nn.hip:110-125 (VnBwdF) into BwdFin, then nn.hip:215-262 (VnBwdBody): combine 3 reads y and writes the interleaved d(P, Q)
+void hc_nn_vn_bwd(const float* dout, const float* in, int combine, long n, int co, const float* scale, const float* shift,
+                  const float* mean, const float* invstd, const float* gamma, int training, float* din, float* dgamma, float* dbeta) {
+    const int lc = combine == 3 ? 0 : combine;
+    const long ld = lc ? 2 * co : co, lddi = combine ? 2 * co : co;
+    std::vector<double> s0, s1;
+    hcnn::colreduce([&](int, int, int) {
+        return [&](long i, int c, double& t0, double& t1) {
+            float yu, yv, a, b;
+            hcnn::vn_load(in, ld, i, c, co, lc, yu, yv);
+            dcnn::vn_bwd_terms(yu, yv, dout[(2 * i) * co + c], dout[(2 * i + 1) * co + c], scale[c], shift[c], mean[c], invstd[c], a, b);
+            t0 = a; t1 = b;
+        };
+    }, n, co, s0, s1);
+    std::vector<float> m1(co), m2(co);
+    for (int c = 0; c < co; ++c) {
+        if (dbeta) dbeta[c] = (float)s0[c];
+        if (dgamma) dgamma[c] = (float)s1[c];
+        m1[c] = (float)(s0[c] / (double)n); m2[c] = (float)(s1[c] / (double)n);
+    }
+    hcnn::tile_walk(n, co, 4, [&](int c) {
+        return [&, c](long i) {
+            float yu, yv, gu, gv;
+            hcnn::vn_load(in, ld, i, c, co, lc, yu, yv);
+            dcnn::vn_bwd_dy(yu, yv, dout[(2 * i) * co + c], dout[(2 * i + 1) * co + c], scale[c], shift[c], mean[c], invstd[c],
+                            (gamma ? gamma[c] : 1.f) * invstd[c], m1[c], m2[c], training, gu, gv);
+            float *ru = din + (2 * i) * lddi, *rv = din + (2 * i + 1) * lddi;
+            if (combine == 2 || combine == 3) { ru[2 * c] = gu; ru[2 * c + 1] = gv; rv[2 * c] = gv; rv[2 * c + 1] = -gu; }
+            else {
+                ru[c] = gu; rv[c] = gv;
+                if (combine) { ru[co + c] = gv; rv[co + c] = -gu; }
+            }
+        };
+    });
+}
+// nn.hip:270-322 (pool_fwd_kernel): 16 row lanes per (cloud, column), then the lanes joined in order with the tie rule
+void hc_nn_pool(const float* h, int B, int N, int C, const float* scale, const float* shift, float slope, int with_mean, float* pooled,
+                int* argmax) {
+    const long ldp = with_mean ? 2 * C : C;
+    for (int cloud = 0; cloud < B; ++cloud)
+        for (int c = 0; c < C; ++c) {
+            float smx[hcnn::RT], ssm[hcnn::RT]; int sam[hcnn::RT];
+            for (int rl = 0; rl < hcnn::RT; ++rl) {
+                float mx = -INFINITY, sm = 0.f; int am = 0;
+                for (int r = rl; r < N; r += hcnn::RT) {
+                    const float y = dcnn::act(fmaf(scale[c], h[((long)cloud * N + r) * C + c], shift[c]), slope);
+                    sm += y;
+                    if (y > mx) { mx = y; am = r; }
+                }
+                smx[rl] = mx; ssm[rl] = sm; sam[rl] = am;
+            }
+            float m = smx[0], t = ssm[0]; int a = sam[0];
+            for (int rr = 1; rr < hcnn::RT; ++rr) {
+                const float v = smx[rr]; const int ar = sam[rr];
+                if (v > m || (v == m && ar < a)) { m = v; a = ar; }
+                t += ssm[rr];
+            }
+            pooled[(long)cloud * ldp + c] = m;
+            if (with_mean) pooled[(long)cloud * ldp + C + c] = t / (float)N;
+            argmax[(long)cloud * C + c] = a;
+        }
+}
+// nn.hip:390-401 (CloudBiasBody); y may be h
+void hc_nn_cloud_bias_add(const float* h, const float* g, long n, int C, long mx, float* y) {
+    for (long r = 0; r < n; ++r)
+        for (int c = 0; c < C; ++c) y[r * C + c] = h[r * C + c] + g[(r / mx) * C + c];
+}
+// nn.hip:406-452, 570-581 (cloud_colsum_kernel, cloud_colsum_final_kernel, cloud_colsum_chunks)
+void hc_nn_cloud_colsum(const float* x, int B, long mx, int C, float* out) {
+    const long coltiles = hcnn::cdivl(C, hcnn::CT * 4);
+    const long want = std::max<long>(1, 768 / std::max<long>(1, B * coltiles));
+    const int chunks = (int)std::max<long>(1, std::min<long>(want, hcnn::cdivl(mx, hcnn::RT)));
+    const int rpc = (int)(hcnn::cdivl(hcnn::cdivl(mx, chunks), hcnn::RT) * hcnn::RT), used = (int)hcnn::cdivl(mx, rpc);
+    for (long cloud = 0; cloud < B; ++cloud)
+        for (int c = 0; c < C; ++c) {
+            std::vector<double> p(used);
+            for (int ch = 0; ch < used; ++ch) {
+                const long r0 = cloud * mx + (long)ch * rpc, r1 = std::min<long>(r0 + rpc, (cloud + 1) * mx);
+                double t = 0;
+                for (int rl = 0; rl < hcnn::RT; ++rl) {
+                    double acc = 0;
+                    for (long r = r0 + rl; r < r1; r += hcnn::RT) acc += (double)x[r * C + c];
+                    t += acc;
+                }
+                p[ch] = t;
+            }
+            double w[64];
+            for (int l = 0; l < 64; ++l) { double t = 0; for (int ch = l; ch < used; ch += 64) t += p[ch]; w[l] = t; }
+            for (int o = 32; o > 0; o >>= 1)
+                for (int l = 0; l < o; ++l) w[l] += w[l ^ o];
+            out[cloud * C + c] = (float)w[0];
+        }
+}
+}
