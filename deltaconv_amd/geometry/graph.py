@@ -127,6 +127,28 @@ class TilePlanT:
 USE_TILE_PLAN = [os.environ.get("DC_TILE_PLAN", "1") != "0"]
 # Transposed applies / max-aggregation backward from the transposed plan (needs the forward plan): A/B switch, same results.
 USE_TILE_PLAN_T = [os.environ.get("DC_TILE_PLAN_T", "1") != "0"]
+# The search behind Graph.knn / geometry.knn_cross where the call names none: "brute" (dc_knn, dc_knn_cross) or "grid" (the exact
+# search over a uniform cell grid, csrc/knn_grid.hip: the same neighbours in the same order, bit for bit).  DC_KNN=brute|grid; no
+# policy picks by size.
+KNN_METHODS = ("brute", "grid")
+KNN_METHOD = [os.environ.get("DC_KNN", "") or "brute"]
+GRID_TARGET = 1.0          # mean points per cell where the call names none (csrc/knn_grid_math.h: DEFAULT_TARGET)
+
+
+def knn_method(fn, method):
+    """The `method` argument of a search, None = the switch -> "brute" | "grid"."""
+    method = KNN_METHOD[0] if method is None else method
+    if method not in KNN_METHODS:
+        raise ValueError(f"{fn}: method = {method!r} (DC_KNN where the call names none), known: {', '.join(KNN_METHODS)}")
+    return method
+
+
+def grid_workspace(num_points, num_clouds, device):
+    """The workspace of one grid search over `num_points` reference rows in `num_clouds` clouds -> (tensor, bytes)."""
+    nbytes = int(lib.raw("dc_knn_grid_workspace_bytes")(int(num_points), int(num_clouds)))
+    if nbytes == 0:
+        raise ValueError(f"grid search: {num_points} points in {num_clouds} clouds are out of range")
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device), nbytes
 
 
 class Graph:
@@ -192,9 +214,15 @@ class Graph:
         return self._tile_plan or None
 
     @staticmethod
-    def knn(pos, k, batch=None, ptr_info=None, lanes_per_query=0):
+    def knn(pos, k, batch=None, ptr_info=None, lanes_per_query=0, method=None, grid_target=None):
         """k nearest neighbours per cloud incl. self (bit-exact order: fp32 ((dx*dx+dy*dy)+dz*dz)
-        ascending, ties by lower index)."""
+        ascending, ties by lower index).  ``method``: "brute" (``dc_knn``: n^2 distances per cloud) or "grid" (``dc_knn_grid``:
+        the same table bit for bit through a uniform cell grid, for large clouds), None = ``KNN_METHOD[0]`` (``DC_KNN``, default
+        "brute").  ``grid_target``: the grid's mean points per cell (None = ``GRID_TARGET``); it cannot change the result.
+        ``lanes_per_query`` picks among the brute-force kernels: with "grid" anything but 0 raises ``ValueError``."""
+        method = knn_method("Graph.knn", method)
+        if method == "grid" and lanes_per_query != 0:
+            raise ValueError("Graph.knn: lanes_per_query picks a brute-force kernel; it cannot be combined with method='grid'")
         require_gpu()
         pos = pos.contiguous().float()
         n = pos.shape[0]
@@ -206,7 +234,13 @@ class Graph:
         if mn < k:
             raise ValueError(f"knn graph: every cloud needs at least k = {k} points, the smallest has {mn}")
         nbr = torch.empty(n, k, dtype=torch.int32, device=pos.device)
-        lib.call("dc_knn", pos, ptr, nc, mx, k, lanes_per_query, nbr)
+        if method == "grid":
+            if n and nc:
+                work, nbytes = grid_workspace(n, nc, pos.device)
+                lib.call("dc_knn_grid", pos, ptr, nc, mx, k, float(GRID_TARGET if grid_target is None else grid_target), nbr, work,
+                         nbytes)
+        else:
+            lib.call("dc_knn", pos, ptr, nc, mx, k, lanes_per_query, nbr)
         return Graph(nbr, ptr, nc, mx, pos=pos)
 
     @staticmethod

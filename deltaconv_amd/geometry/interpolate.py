@@ -16,7 +16,7 @@ __all__ = ["knn_cross", "knn_cross_transpose", "knn_interpolate", "interpolate_r
 
 
 def knn_cross(pos_query, pos_ref, k, ptr_query=None, ptr_ref=None, batch_query=None, batch_ref=None, max_query_cloud=None,
-              out=None):
+              out=None, method=None, grid_target=None):
     """The k nearest points of ``pos_ref`` for every point of ``pos_query``, cloud pair by cloud pair (``torch_cluster.knn``).
 
     pos_query [Nq,3], pos_ref [Nr,3]: DEVICE fp32.  The clouds are given as ``ptr_*`` (int64 [B+1] ABSOLUTE row offsets; a slice
@@ -26,8 +26,15 @@ def knn_cross(pos_query, pos_ref, k, ptr_query=None, ptr_ref=None, batch_query=N
     -> ``(idx int32 [Nq,k], d2 fp32 [Nq,k])``: reference ids LOCAL to the pair's reference cloud in ascending fp32 squared
     distance, ties by the lower id (the order contract of ``knn_graph``); ``-1`` / ``+inf`` where a reference cloud has fewer
     than k points.  A point with a NaN coordinate is never picked.  Rows of ``pos_query`` outside every cloud keep what the
-    buffers held (``-1`` / ``+inf`` when allocated here).  The result carries no autograd graph: positions are not differentiated."""
+    buffers held (``-1`` / ``+inf`` when allocated here).  The result carries no autograd graph: positions are not differentiated.
+
+    ``method``: "brute" (``dc_knn_cross``: Nq x Nr distances per pair) or "grid" (``dc_knn_cross_grid``: the same ``idx`` and ``d2``
+    bit for bit through a uniform cell grid over each reference cloud, for large reference clouds), None = the switch
+    ``geometry.graph.KNN_METHOD[0]`` (``DC_KNN``, default "brute").  ``grid_target``: the grid's mean points per cell (None =
+    ``geometry.graph.GRID_TARGET``); it cannot change the result."""
     from .._lib import lib
+    from . import graph as _graph
+    method = _graph.knn_method("knn_cross", method)
     pos_query, pos_ref = _cross.rows3("knn_cross", "pos_query", pos_query), _cross.rows3("knn_cross", "pos_ref", pos_ref)
     k = int(k)
     if not 1 <= k <= MAX_K:
@@ -46,8 +53,16 @@ def knn_cross(pos_query, pos_ref, k, ptr_query=None, ptr_ref=None, batch_query=N
         return idx, d2
     if pos_ref.shape[0] == 0:                  # every reference cloud is empty: a row that is never read stands in for the null pointer
         pos_ref = pos_ref.new_zeros((1, 3))
+    if method == "grid" and b > 0:
+        target = float(_graph.GRID_TARGET if grid_target is None else grid_target)
+        # the offsets may be a slice of a store's: the reference rows of the call are at most those of pos_ref
+        work, nbytes = _graph.grid_workspace(pos_ref.shape[0], min(b, _cross.MAX_PAIRS), dev)
     for lo, hi in _cross.launches(b):
-        lib.call("dc_knn_cross", pos_query, qptr[lo:hi + 1], pos_ref, rptr[lo:hi + 1], hi - lo, mq, k, idx, d2)
+        if method == "grid":
+            lib.call("dc_knn_cross_grid", pos_query, qptr[lo:hi + 1], pos_ref, rptr[lo:hi + 1], hi - lo, mq, k, target, idx, d2,
+                     work, nbytes)
+        else:
+            lib.call("dc_knn_cross", pos_query, qptr[lo:hi + 1], pos_ref, rptr[lo:hi + 1], hi - lo, mq, k, idx, d2)
     return idx, d2
 
 

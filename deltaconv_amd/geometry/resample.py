@@ -32,7 +32,8 @@ class CloudPair:
     from.  ``frames_fine`` / ``frames_coarse``: ``(normal, x_basis, y_basis)`` over the rows of the respective cloud, as
     ``build_tangent_basis`` returns them behind the normal; without them the vector methods raise ``ValueError``.
     ``max_fine_cloud`` / ``max_coarse_cloud``: the largest cloud of each set where the host knows it; with both given nothing
-    here synchronises (otherwise the constructor reads them from the offsets, once).
+    here synchronises (otherwise the constructor reads them from the offsets, once).  ``search_method``: the ``method`` of both
+    searches (``knn_cross``: "brute" | "grid", None = the ``DC_KNN`` switch); it cannot change a bit of anything held here.
 
     Held, each built on first use and once: the down search (coarse queries into fine references, ``k_down``), the up search
     (fine queries into coarse references, ``k_up``), their transposed lists when ``differentiable`` is set, and the two transport
@@ -45,8 +46,9 @@ class CloudPair:
     returned.  Positions and frames are never differentiated: one that requires grad raises ``RuntimeError``."""
 
     def __init__(self, pos_fine, pos_coarse, ptr_fine, ptr_coarse, k_down=16, k_up=3, frames_fine=None, frames_coarse=None,
-                 differentiable=True, max_fine_cloud=None, max_coarse_cloud=None, non_oriented=True):
+                 differentiable=True, max_fine_cloud=None, max_coarse_cloud=None, non_oriented=True, search_method=None):
         fn = "CloudPair"
+        self.search_method = search_method
         self.k = {"down": int(k_down), "up": int(k_up)}
         for name, k in self.k.items():
             if not 1 <= k <= _cross.MAX_K:
@@ -85,7 +87,8 @@ class CloudPair:
         """-> ``(idx int32 [Nq,k], d2 fp32 [Nq,k])`` of the direction's ``knn_cross``."""
         q, r = self._sides(direction)
         return self._once(("search", direction), lambda: knn_cross(self.pos[q], self.pos[r], self.k[direction], ptr_query=self.ptr[q],
-                                                                   ptr_ref=self.ptr[r], max_query_cloud=self.largest[q]))
+                                                                   ptr_ref=self.ptr[r], max_query_cloud=self.largest[q],
+                                                                   method=self.search_method))
 
     def lists(self, direction):
         """-> ``(tptr, tedge, tcoef)`` of the direction's ``knn_cross_transpose``."""

@@ -84,6 +84,44 @@ int32_t dc_stamp_tag(int32_t record);
 int dc_knn(const float* pos, const int32_t* cloud_ptr, int32_t num_clouds, int32_t max_cloud_size, int32_t k,
            int32_t lanes_per_query, int32_t* nbr, void* stream);
 
+/* ---- exact kNN over a uniform cell grid, for large clouds (csrc/knn_grid.hip, csrc/knn_grid_math.h) ------------------------ */
+/* The workspace of one dc_knn_grid / dc_knn_cross_grid call: linear in the sizes, a function of the sizes alone.
+ *   num_points  HOST: the REFERENCE rows of the call (dc_knn_grid: all points, cloud_ptr[num_clouds] - cloud_ptr[0];
+ *               dc_knn_cross_grid: rptr[B] - rptr[0]);  num_clouds  HOST: the clouds / cloud pairs of the call
+ * -> bytes: one 48-byte grid record per cloud, 2 * num_points + num_clouds per-cell counters and as many cell starts (+ the scan's
+ * block sums), and the points in cell order, 16 bytes each -- about 48 bytes a point.  0: a negative size or more than 2^31 - 1 points. */
+size_t dc_knn_grid_workspace_bytes(int64_t num_points, int32_t num_clouds);
+/* dc_knn through a uniform cell grid per cloud: the arguments and the OUTPUT of dc_knn, bit for bit -- fp32
+ * ((dx*dx+dy*dy)+dz*dz) without contraction, ascending, ties by lower index, self included, global ids; every cloud needs >= k
+ * points; k <= 64.  Opt-in: worth it where the n^2 distances of dc_knn dominate (README: measured), never picked by size here.
+ *   pos, cloud_ptr, num_clouds (<= 65 535), max_cloud_size, k, nbr   as in dc_knn
+ *   target      HOST: the wanted mean number of points per cell (csrc/knn_grid_math.h: make_grid; DEFAULT_TARGET = 1); any positive
+ *               finite value gives the same output -- 1e9 one cell per cloud (a brute-force search on one thread per query), 0.25
+ *               the cap of 2 n cells
+ *   workspace   DEVICE, 16-byte aligned, workspace_bytes >= dc_knn_grid_workspace_bytes(all points of the call, num_clouds)
+ * The grid rule, the ring walk and the proof of the stopping bound: csrc/knn_grid_math.h.  Positions with a non-finite coordinate:
+ * dc_knn's output is meaningless there and this one need not equal it, but it reads and writes in bounds and emits only ids inside
+ * the row's cloud: such a point is never picked, its own row names itself k times, and a slot that no finite point can fill names
+ * the query.  A null pointer, k outside 1 .. 64, num_clouds above 65 535, target not positive and finite, a workspace that is
+ * missing, misaligned or smaller than that of max_cloud_size points: DC_ERR_ARG with a message, checked before anything touches the
+ * device (a workspace smaller than the device-side offsets demand leaves the rows of the clouds past it unwritten).  Seven
+ * launches whose sizes depend on the HOST arguments only, stream-ordered, no allocation, no synchronisation, capturable and
+ * replayable on new positions written in place; integer atomics on counters, and the outputs are a function of the inputs only. */
+int dc_knn_grid(const float* pos, const int32_t* cloud_ptr, int32_t num_clouds, int32_t max_cloud_size, int32_t k, float target,
+                int32_t* nbr, void* workspace, size_t workspace_bytes, void* stream);
+/* dc_knn_cross through a uniform cell grid per REFERENCE cloud: the arguments, limits and OUTPUT of dc_knn_cross (declared with
+ * the propagation stage below), bit for bit in idx and in d2 -- reference ids LOCAL to the pair's reference cloud, ascending d2,
+ * ties by lower id, -1 / +inf where fewer than k reference points can be picked; k <= 16, B <= 65 535.  A reference point with a
+ * non-finite coordinate belongs to no cell and is never picked; a query with one gets -1 / +inf in every slot; a query outside the
+ * box of its reference cloud is searched from the border cell.  The queries are taken as they come (not sorted by cell).
+ *   target, workspace   as in dc_knn_grid, workspace_bytes >= dc_knn_grid_workspace_bytes(rptr[B] - rptr[0], B): the capacity
+ *               in reference rows is read back from workspace_bytes, and it sizes the build's launches
+ * Argument errors as dc_knn_cross, plus target and the workspace as above: DC_ERR_ARG with a message.  B = 0 or
+ * max_query_cloud = 0 returns DC_OK.  Seven launches, stream-ordered, capturable, no allocation, no synchronisation. */
+int dc_knn_cross_grid(const float* query, const int64_t* qptr, const float* ref, const int64_t* rptr, int32_t B,
+                      int64_t max_query_cloud, int32_t k, float target, int32_t* idx, float* d2, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 /* Transposed adjacency of nbr (in-edges per point, ascending edge id).  Stands in for the A^T
  * products torch_sparse autograd performs and torch_scatter's arg-indexed backward. */
 size_t dc_csc_workspace_bytes(int32_t num_points);   /* upper bound for any k <= 255; 4*Nt*(k+1) suffices */
