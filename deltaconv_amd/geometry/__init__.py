@@ -2,6 +2,7 @@ from .operators import *          # noqa: F401,F403
 from .grad_div_mls import *       # noqa: F401,F403
 from .graph import Graph, knn_graph, as_graph  # noqa: F401
 from .utils import batch_dot      # noqa: F401
+from . import fps                                    # noqa: F401  (the module; calling it IS fps.fps: geometry.fps(pos, ...))
 from .fps import geodesic_fps, geodesic_fps_batch    # noqa: F401
 from .mesh_sample import sample_points_batch         # noqa: F401
 from .shape_norm import normalize_shapes_batch       # noqa: F401
@@ -11,4 +12,4 @@ from .connection import *         # noqa: F401,F403
 from .vector_interpolate import *  # noqa: F401,F403
 from .pool import *               # noqa: F401,F403
 from .pool_vectors import *       # noqa: F401,F403
-from .resample import CloudPair, prefix_levels    # noqa: F401
+from .resample import CloudPair, fps_levels, prefix_levels    # noqa: F401

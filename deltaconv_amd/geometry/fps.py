@@ -4,7 +4,10 @@ restatement in deltaconv_amd/csrc_host/fps.cpp behind a C ABI (include/deltaconv
 
 ``geodesic_fps_batch`` is the same sampler for a batch of clouds that already live on the device (csrc/fps.hip behind
 ``dc_geodesic_fps_batch``): the same picks as ``geodesic_fps`` from the same start point, all clouds in two launches.  With
-``large=True`` clouds above that kernel's cap go through ``dc_geodesic_fps_large``, whose distance vector lives in global memory."""
+``large=True`` clouds above that kernel's cap go through ``dc_geodesic_fps_large``, whose distance vector lives in global memory.
+
+``fps`` is plain EUCLIDEAN farthest-point sampling for use inside a training step (csrc/fps_euclid.hip behind ``dc_fps_batch``):
+device offsets, one launch, nothing read on the host, capturable."""
 import ctypes
 import os
 import warnings
@@ -49,6 +52,121 @@ def geodesic_fps(points, n_samples, seed=None):
 FPS_MAX_POINTS = 16384        # DC_FPS_MAX_POINTS: a cloud's distance vector lives in the LDS of one workgroup (csrc/fps_math.h)
 FPS_LARGE_MAX_POINTS = 262144 # DC_FPS_LARGE_MAX_POINTS: the distance vector in global memory, two frontier bit sets in LDS
 FPS_LARGE_POINTS_PER_LAUNCH = 1 << 20   # points of a group of large clouds: its workspace holds 140 bytes per point (140 MiB)
+FPS_EUCLID_MAX_POINTS = 16384 # DC_FPS_EUCLID_MAX_POINTS: a cloud's positions and minima live in the registers of one workgroup
+
+
+def coarse_sizes(ratio, largest, smallest):
+    """(largest, smallest) cloud of the level below one with those: ``ceil(n / ratio)``, the arithmetic of ``prefix_levels``."""
+    return -(-int(largest) // ratio), -(-int(smallest) // ratio)
+
+
+def coarse_offsets(ptr, b, ratio, largest, smallest):
+    """The output offsets of a ``ratio`` level over the int64 device offsets ``ptr`` -> (optr int64 [B+1], rows in all), as
+    ``prefix_levels`` derives them: a uniform batch synchronises nothing, a ragged one reads its total once."""
+    import torch
+    mx, mn = coarse_sizes(ratio, largest, smallest)
+    if largest == smallest:
+        return torch.arange(b + 1, dtype=torch.int64, device=ptr.device) * mx, b * mx
+    optr = torch.zeros(b + 1, dtype=torch.int64, device=ptr.device)
+    optr[1:] = torch.cumsum((ptr[1:] - ptr[:-1] + (ratio - 1)) // ratio, 0)
+    return optr, int(optr[-1])                 # the one host read
+
+
+def fps_launch(pos, ptr, optr, b, max_cloud, max_samples, total, start=None, out=None):
+    """``dc_fps_batch`` on checked arguments: fp32 [N,3] positions, int64 device offsets in and out -> rows int64 [total]."""
+    import torch
+    from .._lib import lib
+    fn = "fps"
+    if max_cloud > FPS_EUCLID_MAX_POINTS:
+        raise ValueError(f"{fn}: a cloud of {max_cloud} points; the sampler takes at most {FPS_EUCLID_MAX_POINTS} per cloud "
+                         "(FPS_EUCLID_MAX_POINTS: a cloud lives in the registers of one workgroup)")
+    if start is not None:
+        if not torch.is_tensor(start) or not start.is_cuda or start.dim() != 1 or start.shape[0] != b or \
+                start.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"{fn}: `start` must be a device int32 / int64 tensor of {b} ids local to their clouds")
+        start = start.to(torch.int32).contiguous()
+    if out is None:
+        out = torch.empty(total, dtype=torch.int64, device=pos.device)
+    elif not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.int64 or tuple(out.shape) != (total,) or \
+            not out.is_contiguous():
+        raise ValueError(f"{fn}: `out` must be a contiguous device int64 tensor of {total} rows")
+    if b and total:
+        lib.call("dc_fps_batch", pos, ptr, optr, b, int(max_cloud), int(max_samples), start, out)
+    return out
+
+
+def fps(pos, ptr=None, batch=None, ratio=None, n_samples=None, start=None, ptr_info=None, out=None):
+    """Euclidean farthest-point sampling of every cloud of a batch on the device, in ONE launch that reads nothing on the host
+    (``torch_cluster.fps(pos, batch, ratio)``; csrc/fps_euclid.hip behind ``dc_fps_batch``).
+
+    pos: DEVICE float32 [N,3].  The clouds: ``ptr_info`` (a ``PtrInfo``: offsets, B, largest cloud, ``min_cloud`` -- nothing is
+    read), or ``ptr`` (B+1 absolute offsets; largest and smallest cloud are read once), or a sorted ``batch`` vector (one read), or
+    one cloud of N rows.  Exactly one of ``ratio`` (an integer >= 1: ``ceil(n_b / ratio)`` picks of cloud b, the sizes of
+    ``prefix_levels``; a ragged batch reads its total once) and ``n_samples`` (that many picks of every cloud; a smaller cloud
+    raises).  ``start``: DEVICE int32 / int64 [B], the first pick of every cloud as an id local to it (an id outside its cloud is
+    read as 0); None starts every cloud at its row 0.
+    -> ``(rows int64 [N_out], optr int64 [B+1])``: ``rows[optr[b] + r]`` is the GLOBAL row of cloud b's pick r, in pick order.
+
+    The rules (csrc/fps_euclid_math.h): the fp32 distance ``(dx*dx + dy*dy) + dz*dz``, a running minimum per point, the next pick
+    is the FIRST index of its maximum; points with a non-finite coordinate are picked last.  The picks are pairwise distinct, a
+    function of the inputs only, and the first m' picks of m are the m'-pick sample -- a cloud whose rows are re-ordered to
+    ``pos[rows]`` samples to the identity prefix, which is what ``prefix_levels`` rests on.  Clouds above
+    ``FPS_EUCLID_MAX_POINTS`` = 16 384 points, empty clouds where the host knows of them, host tensors and anything but float32
+    [N,3] raise ``ValueError``; a ``pos`` that requires grad raises (nothing here is differentiable).  The call can be captured
+    by ``torch.cuda.graph`` when the sizes come from ``ptr_info`` and the batch is uniform or ``n_samples`` is given."""
+    import torch
+    from . import _cross
+    from .graph import _min_cloud, _ptr_from_batch
+    fn = "fps"
+    if not torch.is_tensor(pos) or not pos.is_cuda:
+        raise ValueError(f"{fn}: `pos` must be a tensor on a HIP device (there is no CPU path)")
+    if pos.dim() != 2 or pos.shape[1] != 3 or pos.dtype != torch.float32:
+        raise ValueError(f"{fn}: `pos` must be float32 [N,3], got {pos.dtype} {tuple(pos.shape)}")
+    _cross.no_grad_inputs(fn, pos=pos)
+    if (ratio is None) == (n_samples is None):
+        raise ValueError(f"{fn}: give exactly one of ratio and n_samples")
+    if ratio is not None and (int(ratio) != ratio or int(ratio) < 1):
+        raise ValueError(f"{fn}: ratio must be an integer >= 1, got {ratio!r}")
+    if n_samples is not None and (int(n_samples) != n_samples or int(n_samples) < 1):
+        raise ValueError(f"{fn}: n_samples must be an integer >= 1, got {n_samples!r}")
+    if sum(a is not None for a in (ptr, batch, ptr_info)) > 1:
+        raise ValueError(f"{fn}: give one of ptr, batch and ptr_info")
+    n, dev = int(pos.shape[0]), pos.device
+    if ptr_info is not None:
+        b, mx, mn = int(ptr_info[1]), int(ptr_info[2]), _min_cloud(ptr_info)
+        ptr = ptr_info[0].to(device=dev, dtype=torch.int64).contiguous()
+    elif ptr is not None:
+        ptr = torch.as_tensor(ptr).to(device=dev, dtype=torch.int64).contiguous()
+        if ptr.dim() != 1 or ptr.numel() < 1:
+            raise ValueError(f"{fn}: `ptr` must hold B+1 offsets")
+        b = int(ptr.numel()) - 1
+        sizes = ptr[1:] - ptr[:-1]
+        lo, hi, mn, mx = (torch.stack([ptr[0], ptr[-1], sizes.min(), sizes.max()]).tolist() if b else (0, 0, 1, 1))   # one read
+        if lo < 0 or hi > n:
+            raise ValueError(f"{fn}: `ptr` runs from {lo} to {hi}, `pos` has {n} rows")
+    else:
+        if batch is not None and (not torch.is_tensor(batch) or batch.dim() != 1 or batch.shape[0] != n):
+            raise ValueError(f"{fn}: `batch` must hold one cloud id per row")
+        if n == 0:
+            raise ValueError(f"{fn}: empty cloud")
+        info = _ptr_from_batch(None if batch is None else batch.to(dev), n, dev)
+        ptr, b, mx, mn = info[0].to(torch.int64), int(info[1]), int(info[2]), int(info.min_cloud)
+    if ptr.numel() != b + 1:
+        raise ValueError(f"{fn}: {b} clouds need {b + 1} offsets, got {ptr.numel()}")
+    if b and mn < 1:
+        raise ValueError(f"{fn}: empty cloud")
+    if b and mx > FPS_EUCLID_MAX_POINTS:
+        raise ValueError(f"{fn}: a cloud of {mx} points; the sampler takes at most {FPS_EUCLID_MAX_POINTS} per cloud "
+                         "(FPS_EUCLID_MAX_POINTS: a cloud lives in the registers of one workgroup)")
+    if ratio is not None:
+        optr, total = coarse_offsets(ptr, b, int(ratio), mx, mn)
+        most = coarse_sizes(int(ratio), mx, mn)[0]
+    else:
+        most = int(n_samples)
+        if b and mn < most:
+            raise ValueError(f"{fn}: n_samples = {most}, but a cloud has only {mn} points")
+        optr, total = torch.arange(b + 1, dtype=torch.int64, device=dev) * most, b * most
+    return fps_launch(pos.detach().contiguous(), ptr, optr, b, mx if b else 0, most, total, start, out), optr
 
 
 def fps_starts(sizes, seed=None, first=0):
@@ -172,3 +290,15 @@ def geodesic_fps_batch(pos, ptr, n_samples, start=None, seed=None, large=False):
     if large:
         return _fps_by_size_class(pos.contiguous(), ptr_host, n_samples, start_host)
     return _fps_launches(pos.contiguous(), ptr_host, n_samples, start_host).long()
+
+
+class _CallableModule(type(os)):             # type(os): types.ModuleType
+    """``geometry.fps`` names this module (``geometry.fps.fps_starts``, ``from deltaconv_amd.geometry import fps``) AND the
+    sampler users expect under that name: calling the module is calling ``fps.fps``."""
+
+    def __call__(self, *args, **kwargs):
+        return fps(*args, **kwargs)
+
+
+import sys as _sys  # noqa: E402
+_sys.modules[__name__].__class__ = _CallableModule

@@ -20,7 +20,7 @@ from .pool import _mode, pool_rows, pool_rows_backward
 from .pool_vectors import knn_cross_rotation, pool_vectors, pool_vectors_backward
 from .vector_interpolate import interpolate_vectors, interpolate_vectors_backward, knn_cross_transport
 
-__all__ = ["CloudPair", "prefix_levels"]
+__all__ = ["CloudPair", "fps_levels", "prefix_levels"]
 
 
 class CloudPair:
@@ -251,3 +251,28 @@ def prefix_levels(ptr_info, ratios):
             rows = torch.arange(total, dtype=torch.int64, device=dev) - ptr[of] + levels[0][1][of]
         levels.append((rows, ptr, PtrInfo(ptr.to(torch.int32), b, mx, mn)))
     return levels
+
+
+def fps_levels(pos, ptr_info, ratios, start=None):
+    """``prefix_levels`` for clouds whose rows are in ANY order: the same list of ``(rows, ptr, info)`` with identical ``ptr`` and
+    ``info``, but level 1's ``rows`` are the picks of ONE Euclidean farthest-point sampling launch (``geometry.fps`` with
+    ``ratios[0]``, from ``start`` or every cloud's row 0), in pick order, and the ``rows`` of every deeper level are the prefix of
+    level 1's rows per cloud -- FPS is greedy, so those ARE the coarser samples from the same start.  On clouds already in that
+    pick order the result equals ``prefix_levels``; with no ratios it is ``prefix_levels``.  ``pos``: DEVICE float32 [N,3], the
+    rows of level 0.  A uniform batch synchronises nothing and can be captured."""
+    from .fps import fps_launch
+    levels = prefix_levels(ptr_info, ratios)
+    if len(levels) == 1:
+        return levels
+    if not torch.is_tensor(pos) or not pos.is_cuda or pos.dim() != 2 or pos.shape[1] != 3 or pos.dtype != torch.float32:
+        raise ValueError("fps_levels: `pos` must be a device float32 [N,3] tensor")
+    _cross.no_grad_inputs("fps_levels", pos=pos)
+    if levels[0][2].min_cloud < 1:
+        raise ValueError("fps_levels: empty cloud")
+    prefix1, ptr1, info1 = levels[1]
+    picks = fps_launch(pos.detach().contiguous(), levels[0][1].contiguous(), ptr1.contiguous(), int(ptr_info[1]), levels[0][2][2],
+                       info1[2], int(prefix1.shape[0]), start)
+    # level 1's row of every prefix row: pick r of cloud b stands where the prefix hierarchy has row r of cloud b
+    slot = torch.empty(pos.shape[0], dtype=torch.int64, device=pos.device)
+    slot[prefix1] = torch.arange(prefix1.shape[0], dtype=torch.int64, device=pos.device)
+    return [levels[0], (picks, ptr1, info1)] + [(picks[slot[rows]], ptr, info) for rows, ptr, info in levels[2:]]

@@ -7,28 +7,33 @@ multiscale architecture", experiments/train_shapenet.py:32); the transitions are
 
 Level l + 1 keeps the first ``ceil(n / ratios[l])`` rows of every cloud of level l, with their positions, normals and frames: no
 sampling runs inside the step.  The hierarchy is a farthest-point-sampling hierarchy exactly when the rows of every cloud are in
-FPS pick order, which is where ``geodesic_subsample`` (the dataset recipes) puts them."""
+FPS pick order, which is where ``geodesic_subsample`` (the dataset recipes) puts them.  That is ``sampling="prefix"``, the default.
+With ``sampling="fps"`` one Euclidean farthest-point sampling launch (``geometry.fps_levels``) picks level 1 inside the step and the
+deeper levels are prefixes of its picks: a farthest-point hierarchy on rows in any order."""
 import torch
 
 from .deltanet_base import _ptr_info
 from .deltanet_segmentation import DeltaNetSegmentation
 from ..geometry.graph import Graph, _min_cloud
 from ..geometry.grad_div_mls import build_grad_div, build_tangent_basis, estimate_basis
-from ..geometry.resample import CloudPair, prefix_levels
+from ..geometry.resample import CloudPair, fps_levels, prefix_levels
 from ..nn import DeltaConv
 
 _VECTOR_POOLS = ("interpolate", "max", "mean", "sum", "add")
+_SAMPLINGS = ("prefix", "fps")
 
 
 class DeltaNetMultiscaleBase(torch.nn.Module):
     """``enc_channels[l]``: the widths of the DeltaConv layers of level l on the way down; ``dec_channels[l]``: the width of the
     one DeltaConv that joins level l's encoder output with what comes up from level l + 1; ``ratios[l]``: level l + 1 keeps every
     cloud's first ``ceil(n / ratios[l])`` rows.  ``forward(data)`` -> the list of level-0 scalar features: every output of the
-    level-0 encoder, then the output of the level-0 decoder."""
+    level-0 encoder, then the output of the level-0 decoder.  ``sampling``: ``"prefix"`` (the default) takes the rows as they
+    stand -- a farthest-point hierarchy when they are in FPS pick order; ``"fps"`` runs one Euclidean farthest-point sampling
+    launch per forward pass (``geometry.fps_levels``) and is that hierarchy whatever the order of the rows."""
 
     def __init__(self, in_channels, enc_channels=((64, 64), (128,), (256,)), dec_channels=(128, 128), ratios=(4, 4), mlp_depth=1,
                  num_neighbors=20, k_down=16, k_up=3, grad_regularizer=0.001, grad_kernel_width=1, vector_pool="max",
-                 centralize_first=True):
+                 centralize_first=True, sampling="prefix"):
         super().__init__()
         enc_channels = [list(c) for c in enc_channels]
         levels = len(enc_channels)
@@ -39,6 +44,9 @@ class DeltaNetMultiscaleBase(torch.nn.Module):
                              f"{len(ratios)} and {len(dec_channels)}")
         if vector_pool not in _VECTOR_POOLS:
             raise ValueError(f"DeltaNetMultiscaleBase: vector_pool must be one of {_VECTOR_POOLS}, got {vector_pool!r}")
+        if sampling not in _SAMPLINGS:
+            raise ValueError(f"DeltaNetMultiscaleBase: sampling must be one of {_SAMPLINGS}, got {sampling!r}")
+        self.sampling = sampling
         self.k, self.k_down, self.k_up = int(num_neighbors), int(k_down), int(k_up)
         self.ratios = [int(r) for r in ratios]
         self.grad_regularizer, self.grad_kernel_width, self.vector_pool = grad_regularizer, grad_kernel_width, vector_pool
@@ -80,7 +88,7 @@ class DeltaNetMultiscaleBase(torch.nn.Module):
         else:
             frames = tuple(estimate_basis(pos, Graph.knn(pos, 10, ptr_info=info), orientation=pos))
         levels = []
-        for rows, ptr, linfo in prefix_levels(info, self.ratios):
+        for rows, ptr, linfo in (fps_levels(pos, info, self.ratios) if self.sampling == "fps" else prefix_levels(info, self.ratios)):
             p = pos if rows is None else pos[rows]
             fr = frames if rows is None else tuple(t[rows] for t in frames)
             graph = Graph.knn(p, self.k, ptr_info=linfo)
@@ -127,8 +135,8 @@ class DeltaNetMultiscaleSegmentation(DeltaNetSegmentation):
 
     def __init__(self, in_channels, num_classes, enc_channels=((64, 64), (128,), (256,)), dec_channels=(128, 128), ratios=(4, 4),
                  mlp_depth=1, num_neighbors=20, k_down=16, k_up=3, grad_regularizer=0.001, grad_kernel_width=1, vector_pool="max",
-                 centralize_first=True, embedding_size=1024, categorical_vector=False):
+                 centralize_first=True, embedding_size=1024, categorical_vector=False, sampling="prefix"):
         super().__init__(in_channels, num_classes, embedding_size=embedding_size, categorical_vector=categorical_vector,
                          backbone=DeltaNetMultiscaleBase(in_channels, enc_channels, dec_channels, ratios, mlp_depth, num_neighbors,
                                                          k_down, k_up, grad_regularizer, grad_kernel_width, vector_pool,
-                                                         centralize_first))
+                                                         centralize_first, sampling=sampling))

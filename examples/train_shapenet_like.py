@@ -28,11 +28,13 @@ from deltaconv_amd.data import synthetic_batch
 
 def shapenet_model(args, num_classes):
     """train_shapenet.py:76-89; --multiscale: the multi-resolution network over prefix levels (rows in FPS pick order, as
-    geodesic_subsample writes them, make the levels an FPS hierarchy)."""
+    geodesic_subsample writes them, make the levels an FPS hierarchy); --sampling fps samples level 1 inside every step instead
+    (Euclidean farthest-point sampling, geometry.fps_levels): an FPS hierarchy whatever the order of the rows."""
     if getattr(args, "multiscale", False):
         return DeltaNetMultiscaleSegmentation(in_channels=3, num_classes=num_classes, mlp_depth=2, embedding_size=1024,
                                               num_neighbors=args.k, grad_regularizer=args.grad_regularizer,
-                                              grad_kernel_width=args.grad_kernel, categorical_vector=True)
+                                              grad_kernel_width=args.grad_kernel, categorical_vector=True,
+                                              sampling=getattr(args, "sampling", "prefix"))
     return DeltaNetSegmentation(in_channels=3, num_classes=num_classes, conv_channels=[64, 128, 256], mlp_depth=2,
                                 embedding_size=1024, num_neighbors=args.k, grad_regularizer=args.grad_regularizer,
                                 grad_kernel_width=args.grad_kernel, categorical_vector=True)
@@ -127,6 +129,9 @@ def main(argv=None):
     ap.add_argument("--data", default=None, help="ShapeNet part root (raw/<synset>/*.txt, raw/train_test_split/*.json)")
     ap.add_argument("--multiscale", action="store_true",
                     help="DeltaNetMultiscaleSegmentation: three levels (ratios 4, 4) with transported max-pooling of the vector stream")
+    ap.add_argument("--sampling", choices=("prefix", "fps"), default="prefix",
+                    help="with --multiscale: prefix = the coarser levels are the first rows of every cloud (rows in FPS pick order); "
+                         "fps = Euclidean farthest-point sampling inside the step (rows in any order)")
     ap.add_argument("--device-loader", action="store_true",
                     help="with --data: keep the prepared dataset on the GPU, build and augment every batch in one launch "
                          "(deltaconv_amd.DeviceLoader) instead of per-shape transforms + collate + upload on the host")

@@ -33,6 +33,7 @@ extern "C" {
 #define DC_ERR_WORKSPACE (-3)
 #define DC_FPS_MAX_POINTS (16384) /* points per cloud dc_geodesic_fps_batch takes: 8 bytes of LDS per point in one workgroup */
 #define DC_FPS_LARGE_MAX_POINTS (262144) /* points per cloud dc_geodesic_fps_large takes: two bit sets of n / 8 bytes of LDS */
+#define DC_FPS_EUCLID_MAX_POINTS (16384) /* points per cloud dc_fps_batch takes: 16 points per thread of a 1024-thread workgroup, in registers */
 
 int32_t dc_version(void);
 const char* dc_last_error(void);
@@ -826,6 +827,28 @@ size_t dc_geodesic_fps_large_workspace_bytes(int64_t N);
 int dc_geodesic_fps_large(const void* pos, int32_t pos_is_f64, const int64_t* ptr, int32_t B, int32_t max_cloud_size,
                           int32_t n_samples, const int32_t* start, int32_t* out, void* workspace, size_t workspace_bytes,
                           void* stream);
+
+/* ---- Euclidean farthest-point sampling inside the step (csrc/fps_euclid.hip, csrc/fps_euclid_math.h) -------------------------- */
+/* What torch_cluster.fps(pos, batch, ratio) and the set abstraction of PointNet++ do, for B clouds in ONE launch that reads
+ * nothing on the host (the reference ships only the geodesic sampler of its data preparation, deltaconv/transforms/
+ * geodesic_fps.py:14-43; its multi-resolution hint is experiments/train_shapenet.py:32).  Rules (csrc/fps_euclid_math.h): the
+ * contract's fp32 distance (dx*dx + dy*dy) + dz*dz, every operation rounded on its own; a running minimum per point; the next
+ * pick is the FIRST index of its maximum; a point with a non-finite coordinate is picked only after every finite one, in
+ * ascending id.  The picks are pairwise distinct and a function of the inputs only; the first m' picks of m are the m'-pick sample.
+ *   pos        DEVICE [N,3] contiguous fp32
+ *   ptr        DEVICE [B+1] ABSOLUTE row offsets of the clouds into pos
+ *   optr       DEVICE [B+1] offsets into rows: cloud b asks for optr[b+1] - optr[b] picks (at most max_samples are written)
+ *   max_cloud  HOST: >= the largest cloud, <= 16 384 (DC_FPS_EUCLID_MAX_POINTS: a cloud's positions and minima live in the
+ *              registers of one workgroup); it alone picks the kernel instance.  Of a larger cloud only the first rows are sampled
+ *   max_samples  HOST: >= the most picks any cloud asks for
+ *   start      DEVICE [B] first pick of every cloud, local to the cloud, or NULL for row 0; an id outside its cloud is read as 0
+ *   rows       DEVICE [optr[B]]: rows[optr[b] + r] = ptr[b] + pick_r, a GLOBAL row id, in pick order; a pick index r at or above
+ *              the cloud's size gets -1
+ * A null pointer (pos, ptr, optr, rows), B < 0, max_samples < 0 or max_cloud outside 0 .. 16 384: DC_ERR_ARG with a message;
+ * B = 0 returns DC_OK.  No workspace, no atomics; launch sizes depend on B and max_cloud alone, so the call can be captured and a
+ * captured call replays on positions written in place.  Stream-ordered. */
+int dc_fps_batch(const float* pos, const int64_t* ptr, const int64_t* optr, int32_t B, int32_t max_cloud, int32_t max_samples,
+                 const int32_t* start, int64_t* rows, void* stream);
 
 /* ---- surface sampling of a batch of triangle meshes (csrc/mesh.hip, csrc/mesh_math.h) ------------------------------------------ */
 /* Bytes of workspace dc_mesh_sample needs for meshes of F_total faces in all: the cdf, 8 bytes per face.  Reference:

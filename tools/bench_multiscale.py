@@ -2,9 +2,12 @@
 the same batch: forward + loss + backward + SGD update replayed from a HIP graph (``GraphedTrainStep``).  Reported per model: the
 library launches of one eager step (calls through the C ABI; torch's own kernels are not counted), ms per step (HIP events
 around ``--steps`` back-to-back replays, ``--repeats`` times, legs alternating) and the run-to-run spread.  Descriptive: the two
-networks do different work and neither is expected to beat the other.  Needs an MI355X.
+networks do different work and neither is expected to beat the other.  ``--sampling fps`` adds the multi-resolution step with
+``sampling="fps"`` (one Euclidean farthest-point sampling launch inside the captured step, ``geometry.fps_levels``) as a third
+leg and reports its cost against the ``"prefix"`` step of the same run.  Needs an MI355X.
 
     python tools/bench_multiscale.py --out profiles/device_multiscale.txt
+    python tools/bench_multiscale.py --sampling fps --out profiles/device_multiscale_fps.txt
 """
 import argparse
 import os
@@ -28,6 +31,8 @@ def main():
     ap.add_argument("--k", type=int, default=20)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--sampling", choices=("prefix", "fps"), default="prefix",
+                    help="fps: a third leg, the multi-scale step with sampling=\"fps\", against the prefix step of this run")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -47,6 +52,10 @@ def main():
         "single resolution (conv_channels [64, 128, 256], mlp_depth 2)":
             lambda: dc.models.DeltaNetSegmentation(3, args.classes, num_neighbors=args.k),
     }
+    prefix_name = next(iter(models))
+    fps_name = "multi-scale, sampling=\"fps\" (the same network; level 1 sampled inside the step)"
+    if args.sampling == "fps":
+        models[fps_name] = lambda: dc.models.DeltaNetMultiscaleSegmentation(3, args.classes, num_neighbors=args.k, sampling="fps")
     say(f"# captured training steps on {torch.cuda.get_device_name(0)}: {args.clouds} clouds of {args.points} points, k = {args.k}, "
         f"{args.classes} classes; ms per step = HIP events around {args.steps} back-to-back replays, {args.repeats} repeats, the "
         f"models alternating")
@@ -82,6 +91,11 @@ def main():
         med = sorted(t)[len(t) // 2]
         say(f"{name}: " + ", ".join(f"{x:.3f}" for x in t) + f" ms / step; median {med:.3f} ms, spread (max - min) "
             f"{max(t) - min(t):.3f} ms = {(max(t) - min(t)) / med * 100:.2f} %")
+    if args.sampling == "fps":
+        med = {name: sorted(t)[len(t) // 2] for name, t in times.items()}
+        spread = max(max(times[n]) - min(times[n]) for n in (prefix_name, fps_name))
+        say(f"sampling=\"fps\" against sampling=\"prefix\" (medians of this run): {med[fps_name] - med[prefix_name]:+.3f} ms / step = "
+            f"{(med[fps_name] / med[prefix_name] - 1) * 100:+.2f} %; the larger spread of the two legs is {spread:.3f} ms")
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as fh:
