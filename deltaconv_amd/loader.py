@@ -322,6 +322,24 @@ class DeviceDataset:
         return DeviceDataset(take(self.pos), ptr, np.full(s, m, dtype=np.int64), take(self.norm), take(self.x), take(self.y_point),
                              self.y_cloud, self.category)
 
+    def voxel_subsample(self, size, origin=None, pick="centre"):
+        """A new store that keeps of every cloud one point per occupied grid cell of edge ``size`` (``geometry.voxel_subsample``:
+        the member nearest the cell centre, or with ``pick="first"`` the first one; ``origin=None``: every cloud's grid starts at
+        its own minimum, so a cloud thins the same way in any store).  ``pos``, ``norm``, ``x`` and per-point ``y`` are gathered by
+        the kept rows, which stay in their order; ``y_cloud`` and ``category`` are shared; the ragged host ``sizes`` come from the
+        output offsets.  Two more attributes: ``source_rows`` (int64 [N_out]: the kept rows of THIS store) and ``cluster`` (int64
+        [N]: for every row of this store the row of the new one that stands for it, -1 for a row with a non-finite coordinate) --
+        ``Propagator(sub, parent)`` interpolates predictions back, ``cluster`` pools onto the thinned store.  Linear in the
+        points: it evens out a scan or an over-tessellated mesh before ``geodesic_subsample``.  Two device reads: the call's own and the output offsets."""
+        from .geometry.voxel import voxel_subsample
+        rows, optr, cluster = voxel_subsample(self.pos, size, ptr=self.ptr, origin=origin, pick=pick)
+        take = lambda t: None if t is None else t[rows].contiguous()
+        optr_host = optr.cpu().numpy()
+        sub = DeviceDataset(take(self.pos), optr, optr_host[1:] - optr_host[:-1], take(self.norm), take(self.x), take(self.y_point),
+                            self.y_cloud, self.category)
+        sub.source_rows, sub.cluster = rows, cluster
+        return sub
+
 
 def epoch_permutation(n, seed, epoch, shuffle=True):
     """The order of the n clouds in `epoch`: a function of (seed, epoch) only; ``arange`` without shuffling."""

@@ -18,6 +18,7 @@ are the reference's.
     python examples/train_shapeseg_like.py --epochs 2                          # synthetic labelled meshes
     python examples/train_shapeseg_like.py --data /data/ShapeSeg --epochs 50   # raw/ShapeSeg/<SET>/raw/{meshes,segs}
     python examples/train_shapeseg_like.py --epochs 2 --vertex-clouds          # vertices + vertex normals, no surface sampling
+    python examples/train_shapeseg_like.py --epochs 2 --vertex-clouds --voxel-size 0.02   # one vertex per grid cell, then geodesic FPS
 """
 import argparse
 import json
@@ -57,8 +58,10 @@ def prepare(items, dev, args):
     if meshes.degenerate.any():
         raise SystemExit(f"{int(meshes.degenerate.sum())} meshes without surface area or extent: nothing to normalise them by")
     if args.vertex_clouds:
-        return meshes.vertex_cloud().geodesic_subsample(args.num_points, seed=args.seed,
-                                                        large="device" if args.device_fps_large else "host")
+        cloud = meshes.vertex_cloud()
+        if args.voxel_size is not None:                 # one vertex per grid cell first: linear, and it evens out the tessellation
+            cloud = cloud.voxel_subsample(args.voxel_size)
+        return cloud.geodesic_subsample(args.num_points, seed=args.seed, large="device" if args.device_fps_large else "host")
     return meshes.sample_points(args.num_points * args.sampling_margin, include_normals=True, include_labels=True,
                                 seed=args.seed).geodesic_subsample(args.num_points, seed=args.seed)
 
@@ -78,6 +81,9 @@ def main(argv=None):
     ap.add_argument("--device-fps-large", action="store_true",
                     help="with --vertex-clouds: meshes of more than 16 384 vertices are reduced on the device too "
                          "(geodesic_subsample(large='device'), up to 262 144 vertices) instead of through the host library")
+    ap.add_argument("--voxel-size", type=float, default=None,
+                    help="with --vertex-clouds: thin every vertex cloud to one vertex per grid cell of this edge length "
+                         "(DeviceDataset.voxel_subsample; the meshes are normalised to about unit extent) before the geodesic sampling")
     ap.add_argument("--layers", type=int, default=8, help="convolution layers (train_shapeseg.py:71: 8)")
     ap.add_argument("--channels", type=int, default=128, help="channels of every layer (train_shapeseg.py:71: 128)")
     ap.add_argument("--seed", type=int, default=1, help="of the split, the surface samples, the FPS starts and the loader")
@@ -90,6 +96,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.device_fps_large and not args.vertex_clouds:
         raise SystemExit("--device-fps-large samples the vertex clouds of --vertex-clouds: it needs --vertex-clouds")
+    if args.voxel_size is not None and not args.vertex_clouds:
+        raise SystemExit("--voxel-size thins the vertex clouds of --vertex-clouds: it needs --vertex-clouds")
 
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)

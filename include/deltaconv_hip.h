@@ -850,6 +850,43 @@ int dc_geodesic_fps_large(const void* pos, int32_t pos_is_f64, const int64_t* pt
 int dc_fps_batch(const float* pos, const int64_t* ptr, const int64_t* optr, int32_t B, int32_t max_cloud, int32_t max_samples,
                  const int32_t* start, int64_t* rows, void* stream);
 
+/* ---- voxel-grid subsampling of device-resident clouds (csrc/voxel.hip, csrc/voxel_math.h) --------------------------------------- */
+/* The workspace of one dc_voxel_subsample call: a function of the sizes alone, linear -- 2 * num_points + num_clouds table slots of
+ * 16 bytes, the scan of num_points + 1 entries (+ its block sums), 12 bytes of origin per cloud: about 40 bytes a point.
+ * 0: a negative size, more than 2^31 - 1 points or more than 2^24 clouds. */
+size_t dc_voxel_subsample_workspace_bytes(int64_t num_points, int32_t num_clouds);
+/* What torch_cluster.grid_cluster / torch_geometric.nn.voxel_grid followed by consecutive_cluster compute, plus a representative
+ * per cell: one point per occupied cell of edge `size` of every cloud, and for every point the output row of its cell.  The rules
+ * (csrc/voxel_math.h): a point takes part iff its coordinates are finite; the origin of a cloud is the fp32 minimum over ITS finite
+ * points (a cloud's result does not depend on its batch-mates) or the caller's; per axis the cell is floorf(fl(fl(p - o) / s));
+ * the representative of a cell is the member with the smallest key (bits(d2) << 32 | local index), d2 the contract's fp32
+ * (dx*dx + dy*dy) + dz*dz to the cell centre fl(fl(fl(t + 0.5) * s) + o) (pick 0) or 0 (pick 1: the first member); the
+ * representatives of a cloud come in ascending row order.  A function of the inputs only: the same bits on every run.
+ *   pos         DEVICE [num_points,3] contiguous fp32
+ *   ptr         DEVICE [B+1] row offsets of the clouds into pos; rows outside every cloud belong to no cell
+ *   num_points  HOST: the rows of pos (it sizes the workspace and, with B, every launch);  B <= 2^24
+ *   size_x/y/z  HOST: the edge lengths, positive and finite
+ *   origin      DEVICE [B,3] fp32, or NULL for every cloud's own minimum
+ *   pick        HOST: 0 = the member nearest the cell centre, 1 = the first member
+ *   rows        DEVICE [num_points] (capacity; scratch of the scan until the last launch): the first info[0] entries are the
+ *               representatives' rows of pos, clouds in order, ascending inside a cloud
+ *   optr        DEVICE [B+1]: cloud b's representatives are rows[optr[b] .. optr[b+1])
+ *   cluster     DEVICE [num_points]: the output row of the point's cell (rows[cluster[i]] is i's representative), -1 for a point
+ *               that belongs to no cell
+ *   info        DEVICE [4]: [0] the output rows in all; [1] the first cloud with a finite point whose cell index reaches 2^20 in
+ *               magnitude on some axis (its cell does not pack into 63 bits; such a point gets no cell and the outputs are not to
+ *               be used), -1 for none; [2] non-zero if a cloud's table slice ran out (cannot happen for offsets that ascend);
+ *               [3] 0
+ *   workspace   DEVICE, 16-byte aligned, workspace_bytes >= dc_voxel_subsample_workspace_bytes(num_points, B)
+ * A null pointer, a size that is not positive and finite, pick outside {0, 1}, B or num_points out of range, a workspace that is
+ * missing, misaligned or too small: DC_ERR_ARG with a message, before anything touches the device.  Seven launches (six with an
+ * origin) whose sizes depend on num_points and B alone, stream-ordered, no allocation, no synchronisation; 64-bit integer atomics
+ * (compare-and-swap on cells, minimum on keys) in an open-addressing table of which every cloud owns a slice -- the probe loop is
+ * bounded by the slice and never waits on another thread, and table collisions cannot reach the outputs. */
+int dc_voxel_subsample(const float* pos, const int64_t* ptr, int32_t B, int64_t num_points, float size_x, float size_y,
+                       float size_z, const float* origin, int32_t pick, int64_t* rows, int64_t* optr, int64_t* cluster,
+                       int64_t* info, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- surface sampling of a batch of triangle meshes (csrc/mesh.hip, csrc/mesh_math.h) ------------------------------------------ */
 /* Bytes of workspace dc_mesh_sample needs for meshes of F_total faces in all: the cdf, 8 bytes per face.  Reference:
  * deltaconv/transforms/sample_points.py:22-59 (the area vector of :29-32 is the only state between its stages). */
