@@ -35,6 +35,10 @@
 // this kernel's split loop); 64-row tiles, ragged shapes, the exact chain and switch DC_OPT_TN_PLANES = 1 run this kernel
 // (dc_tn_lds_launch below).
 //
+// Plain products over pre-split weight planes (BP, no prologue) bring their activation tiles into LDS by 16-byte LDS-DMA instead:
+// a ring of three unpadded [BM][32] buffers, chunk-swizzled through the source addresses, counted vmcnt waits (DMA = 1 below;
+// switch DC_OPT_GEMM_A_REGS = 1: the register-staged loop; same bits; DESIGN.md section 3.3, profiles/gemm_dma_ab.txt).
+//
 // Fused epilogues (forward): the per-column sum / sum of squares of the tile (BatchNorm statistics of the
 // Linear output, nn/nonlin.py:24-35), or of the per-point vector norms of an interleaved (P_c, Q_c) output
 // (VectorNonLin statistics, nn/nonlin.py:63-79) are reduced in fp64 inside the workgroup and written as one
@@ -58,6 +62,9 @@ using namespace dcsplit;
 
 #ifndef DC_X3_PLAIN
 #define DC_X3_PLAIN 2          // split-product loop of the plain products: 1 = simple, 2 = pipelined (two plane sets)
+#endif
+#ifndef DC_BP_UNIFORM_WAVE
+#define DC_BP_UNIFORM_WAVE 1   // plane-fed kernels: the wave index as a scalar (0: as computed from threadIdx -- A/B builds)
 #endif
 #ifndef DC_X3_PRO
 #define DC_X3_PRO 1            // ... of the BatchNorm-backward prologue variants (no registers for a second plane set)
@@ -134,9 +141,10 @@ __device__ __forceinline__ void split8(const f32x4 a, const f32x4 b, Planes& o) 
         o.h[j] = h; o.m[j] = m; o.l[j] = l;
     }
 }
-template <int BM, int BN, int AL, int BL, int MODE, int EPI, int PRO = 0, int X3 = 0, int BP = 0>
+template <int BM, int BN, int AL, int BL, int MODE, int EPI, int PRO = 0, int X3 = 0, int BP = 0, int DMA = 0>
 __device__ __forceinline__ void gemm_body(const GemmP& p, const unsigned bid, const unsigned gemm_blocks) {
     static_assert(!BP || (X3 == 2 && AL == A_MK && BL == B_NK && MODE == 0), "pre-split B planes: pipelined split loop, K-contiguous operands, whole tiles");
+    static_assert(!DMA || (BP && !PRO), "LDS-DMA activation ring: plain products over pre-split weight planes only");
     constexpr bool FAST = MODE == 0;               // no guards anywhere (loads, statistics, stores)
     // guarded modes per operand: 1 = 16-byte loads, 2 = dword loads.  MODE 1: both vector, 2: both scalar, 3: A vector /
     // B scalar, 4: A scalar / B vector
@@ -150,7 +158,12 @@ __device__ __forceinline__ void gemm_body(const GemmP& p, const unsigned bid, co
     float* As = smem;                  // [2][A_FL]
     float* Bs = smem + 2 * A_FL;       // [2][B_FL]
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // (DC_BP_UNIFORM_WAVE: the wave index of the plane-fed kernels as a scalar.  The plane loads' soffset depends on the wave's
+    //  column block; computed from threadIdx it is a vector value to the compiler, which wraps EVERY plane load in a readfirstlane
+    //  loop -- 60 of them in the 128 x 128 kernel, each a basic block of its own in the middle of the pinned stream.  Same
+    //  addresses, same bits; whole step -1.4 %, profiles/gemm_dma_ab.txt)
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = (BP && DC_BP_UNIFORM_WAVE) ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     const int li = lane & 31, lh = lane >> 5;
     // Phase shift.  The two workgroups of a CU start together and stay in lockstep: both in the K loop (sharing the
     // matrix pipe, each at half speed -- one wave per SIMD already saturates it), then both in the epilogue / the next
@@ -264,6 +277,27 @@ __device__ __forceinline__ void gemm_body(const GemmP& p, const unsigned bid, co
                 *reinterpret_cast<f32x4*>(b + (idx / (BN / 4)) * BN + (idx % (BN / 4)) * 4) = sb[S][it];
         }
     };
+    // DMA: the A tile of a K tile goes global -> LDS by 16-byte LDS-DMA (buffer_load_dwordx4 ... lds), no staging registers and
+    // no ds_write.  One instruction of a wave writes 64 x 16 bytes = 1 KiB = 8 whole rows of 32 floats from a wave-uniform LDS base
+    // (M0), so the ring buffers are [BM][32] WITHOUT padding and the 16-byte chunks of a row are permuted through the lanes' own
+    // SOURCE addresses instead: LDS chunk position cp of row r holds global chunk cp ^ ((r >> 1) & 7) (the 8 lanes of a row still
+    // read one whole 128-byte line; fragment reads below; banks: tools/gemm_dma_layout_sim.py).  Piece `it` of wave w = rows
+    // 32 it + 8 w .. + 7 -- the rows the register path gives the same threads.  `live` == false (tile past the reduction range):
+    // a descriptor of zero records, the range check drops the access while the instruction still counts on vmcnt -- no branch in
+    // the pinned stream and every wait below counts the same number of pieces.
+    constexpr int A_RB = BM * BK;                                            // floats per ring buffer
+    static_assert(!DMA || 3 * A_RB <= (2 * (A_FL + B_FL) > BM * BN ? 2 * (A_FL + B_FL) : BM * BN),
+                  "the ring of three A buffers lives in what lds_bytes() already allocates (the B half is unused under BP)");
+    const unsigned voa_dma = (unsigned)(((tid >> 3) * p.lda + (((tid & 7) ^ ((tid >> 4) & 7)) << 2)) * 4);
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    auto dma_tile_pieces = [&](int first, int count, int buf, long k0, bool live) {
+        const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.A + m0 * p.lda + k0), 0,
+                                                                            live ? 0x7FFFFFFF : 0, 0x00020000);
+#pragma unroll
+        for (int it = first; it < first + count; ++it)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)(As + buf * A_RB + (it * 32 + wave_u * 8) * BK),
+                                                     16, (int)voa_dma, (int)((unsigned)(it * 32 * 4) * (unsigned)p.lda), 0, 0);
+    };
     // Fragments: lane (li, lh) holds k = 8 j + 4 lh + t (t = 0..3) of fragment set j for its row / column -- one
     // ds_read_b128 on a K-contiguous tile, four ds_read_b32 on a reduction-major one.  Two register sets.
     f32x4 fa[2][TM], fb[2][TN];
@@ -309,10 +343,19 @@ __device__ __forceinline__ void gemm_body(const GemmP& p, const unsigned bid, co
         // splits on the VALU while the other feeds the matrix pipe).
         f32x4 qa[TM][2], qb[TN][2];
         Planes pa[TM], pb[TN];
+        // DMA ring: the two 16-byte chunks c = 4 ks + 2 lh (+ 1) of the lane's row sit at chunk positions c ^ ((row >> 1) & 7)
+        // (wm0 + 32 i is a multiple of 32: the row's swizzle is the lane's).  The 16 rows of a ds_read_b128 lane group then cover
+        // all sixteen 16-byte slots of the 256-byte bank row: slot = 8 (row & 1) + (c ^ ((row >> 1) & 7)).
+        auto a_chunk = [&](int buf, int i, int ks, int half) -> const f32x4* {
+            return reinterpret_cast<const f32x4*>(As + buf * A_RB + (wm0 + 32 * i + li) * BK + (((4 * ks + 2 * lh + half) ^ ((li >> 1) & 7)) << 2));
+        };
         auto read_raw = [&](int buf, int ks) {
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
-                if (AL == A_MK) {
+                if (DMA) {
+                    qa[i][0] = *a_chunk(buf, i, ks, 0);
+                    qa[i][1] = *a_chunk(buf, i, ks, 1);
+                } else if (AL == A_MK) {
                     const float* a = As + buf * A_FL + (wm0 + 32 * i + li) * LDK + 16 * ks + 8 * lh;
                     qa[i][0] = *reinterpret_cast<const f32x4*>(a);
                     qa[i][1] = *reinterpret_cast<const f32x4*>(a + 4);
@@ -394,7 +437,10 @@ __device__ __forceinline__ void gemm_body(const GemmP& p, const unsigned bid, co
             auto read_frag = [&](int f, int buf, int ks) {
                 if (f < TM) {
                     const int i = f;
-                    if (AL == A_MK) {
+                    if (DMA) {
+                        qa[i][0] = *a_chunk(buf, i, ks, 0);
+                        qa[i][1] = *a_chunk(buf, i, ks, 1);
+                    } else if (AL == A_MK) {
                         const float* a = As + buf * A_FL + (wm0 + 32 * i + li) * LDK + 16 * ks + 8 * lh;
                         qa[i][0] = *reinterpret_cast<const f32x4*>(a);
                         qa[i][1] = *reinterpret_cast<const f32x4*>(a + 4);
@@ -469,14 +515,37 @@ __device__ __forceinline__ void gemm_body(const GemmP& p, const unsigned bid, co
                             __builtin_amdgcn_sched_group_barrier(0x002, BP ? 36 * NF / NM : VPM, 0); // its share of the split
                         }
                     }
+                    if constexpr (DMA) {
+                        // no LDS stores; the DMA pieces of a staging step ride behind its A slots, i.e. behind ALL of the step's
+                        // plane loads (the wait accounting at tile_steps depends on that order)
+                        if (!std::is_void_v<decltype(stage(0))> && f >= TN) __builtin_amdgcn_sched_group_barrier(0x020, A_IT / TM, 0);
+                    } else {
                     if (PRO) {                                                               // LDS stores of the group
                         if (f == 0) __builtin_amdgcn_sched_group_barrier(0x200, NST, 0);
                     } else {
                         __builtin_amdgcn_sched_group_barrier(0x200, (NST + NF - 1) / NF, 0);
                     }
                     __builtin_amdgcn_sched_group_barrier(0x020, (NLD + NF - 1) / NF, 0);     // global loads of the group
+                    }
                 }
             };
+            if constexpr (DMA) {
+                // Ring of three A buffers: tile t lives in buffer t % 3.  Tiles 0, 1, 2 are requested here (3 A_IT pieces, the ones
+                // of tiles that do not exist dropped by the range check); the fragment reads below and in tile 0 need tiles 0 and 1.
+                // Issue order = the loop's (plane loads of two k-steps, then the A_IT pieces of the newest tile), so the loop is
+                // entered in its steady state: vmcnt retires in order, and the wait leaves exactly the 6 TN plane loads and the
+                // pieces of tile 2 outstanding.  (sched_barrier: no plane load may move in front of a piece of tiles 0 / 1.)
+                dma_tile_pieces(0, A_IT, 0, kbeg, true);
+                dma_tile_pieces(0, A_IT, 1, kbeg + (long)min(1, nk - 1) * BK, nk > 1);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int jn = 0; jn < TN; ++jn) load_bp(jn, pb[jn], kbeg);
+#pragma unroll
+                for (int jn = 0; jn < TN; ++jn) load_bp(jn, pb1[jn], kbeg + 16);
+                dma_tile_pieces(0, A_IT, 2, kbeg + (long)min(2, nk - 1) * BK, nk > 2);
+                __builtin_amdgcn_sched_barrier(0);
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(6 * TN + A_IT) : "memory");
+            } else {
 #pragma unroll
             for (int n = 0; n < NLD; ++n) load_piece(n, kbeg, S0{});
 #pragma unroll
@@ -491,11 +560,12 @@ __device__ __forceinline__ void gemm_body(const GemmP& p, const unsigned bid, co
 #pragma unroll
                 for (int n = 0; n < NLD; ++n) load_piece(n, kbeg + 2 * BK, S0{});
             }
+            }
             lds_barrier();
             DC_STAMP(7);
             read_raw(0, 0);
             split_all();
-            if (BP) {                                       // the planes of the first two k-steps
+            if (BP && !DMA) {                               // the planes of the first two k-steps
 #pragma unroll
                 for (int jn = 0; jn < TN; ++jn) load_bp(jn, pb[jn], kbeg);
                 if (RING3) {
@@ -507,8 +577,12 @@ __device__ __forceinline__ void gemm_body(const GemmP& p, const unsigned bid, co
             // one K tile = two k-steps.  ba / bb: the B plane sets the two steps multiply; la / lb: the sets they PREPARE -- in the
             // in-loop form the set of the next step (cut from the fragments in flight), with pre-split planes (BP) the set of the
             // step after next, loaded from global memory: a ring of three sets, two k-steps of MFMAs over every L2 round trip
-            auto tile_steps = [&](int kt, const Planes (&ba)[TN], const Planes (&bb)[TN], Planes (&la)[TN], Planes (&lb)[TN]) {
+            // (DMA: phase_tag = kt % 3, static -- the ring buffer the step's pieces fill; the fragments come from the next one)
+            auto tile_steps = [&](int kt, const Planes (&ba)[TN], const Planes (&bb)[TN], Planes (&la)[TN], Planes (&lb)[TN],
+                                  auto phase_tag) {
+                constexpr int PH = decltype(phase_tag)::value;
                 const int cur = kt & 1;
+                const int rbuf = DMA ? (PH + 1) % 3 : cur ^ 1;
                 // (unconditional: past the last tiles the stores refill a buffer nobody reads again and the loads re-read the last
                 // tile -- no branches inside the pinned instruction stream)
                 const long k3 = kbeg + (long)min(kt + 3, nk - 1) * BK;
@@ -529,6 +603,13 @@ __device__ __forceinline__ void gemm_body(const GemmP& p, const unsigned bid, co
 #pragma unroll
                     for (int n = f * NLD / NF; n < (f + 1) * NLD / NF; ++n) load_piece(n, k3, S0{});
                 };
+                // DMA: the A_IT pieces of tile kt + 3 -> buffer kt % 3 (tile kt: every read of it returned before the barrier that
+                // ended tile kt - 1), in the A slots of the second step = behind all 6 TN plane loads of this tile
+                auto pieces = [&](int f) {
+                    if (f >= TN) dma_tile_pieces((f - TN) * (A_IT / TM), A_IT / TM, PH, k3, kt + 3 < nk);
+                    return 0;
+                };
+                (void)pieces; (void)stores_loads;
                 // (the weight gradient's reduction-major form spills with the pieces inside the stream: it keeps the burst behind it)
                 constexpr bool INSIDE = AL == A_MK;
                 // (BP: the planes requested now belong to tile kt + 1 -- ring of three sets -- or, where the prologue's registers
@@ -536,9 +617,18 @@ __device__ __forceinline__ void gemm_body(const GemmP& p, const unsigned bid, co
                 const long kn = kbeg + (long)min(kt + 1, nk - 1) * BK;
                 const long kb1 = RING3 ? kn : kbeg + (long)kt * BK + 16, kb2 = RING3 ? kn + 16 : kn;
                 __builtin_amdgcn_sched_barrier(0);
-                step(pa, ba, pa1, la, cur ^ 1, 0, none, kb1);
+                step(pa, ba, pa1, la, rbuf, 0, none, kb1);
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (INSIDE) {
+                if constexpr (DMA) {
+                    step(pa1, bb, pa, lb, rbuf, 1, pieces, kb2);
+                    // Tile kt + 1 is multiplied from fragments read during this tile, so tile kt + 2 (requested in tile kt - 1, or
+                    // in front of the loop) must be in LDS behind the barrier below.  Issue order since those pieces: the 6 TN plane
+                    // loads of this tile, then its A_IT pieces (tile kt + 3) -- exactly these stay outstanding.  (The compiler's own
+                    // counted waits on the plane registers never reach a piece sooner: the planes loaded after the pieces of tile
+                    // kt + 2 are this tile's, first multiplied in tile kt + 1.)
+                    __builtin_amdgcn_sched_barrier(0);
+                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(6 * TN + A_IT) : "memory");
+                } else if constexpr (INSIDE) {
                     step(pa1, bb, pa, lb, cur ^ 1, 1, stores_loads, kb2);
                 } else {
                     step(pa1, bb, pa, lb, cur ^ 1, 1, none);
@@ -558,14 +648,14 @@ __device__ __forceinline__ void gemm_body(const GemmP& p, const unsigned bid, co
             if constexpr (RING3) {
                 int kt = 0;
                 for (; kt + 3 <= nk; kt += 3) {
-                    tile_steps(kt, pb, pb1, pb2, pb);
-                    tile_steps(kt + 1, pb2, pb, pb1, pb2);
-                    tile_steps(kt + 2, pb1, pb2, pb, pb1);
+                    tile_steps(kt, pb, pb1, pb2, pb, std::integral_constant<int, 0>{});
+                    tile_steps(kt + 1, pb2, pb, pb1, pb2, std::integral_constant<int, 1>{});
+                    tile_steps(kt + 2, pb1, pb2, pb, pb1, std::integral_constant<int, 2>{});
                 }
-                if (kt < nk) tile_steps(kt, pb, pb1, pb2, pb);
-                if (kt + 1 < nk) tile_steps(kt + 1, pb2, pb, pb1, pb2);
+                if (kt < nk) tile_steps(kt, pb, pb1, pb2, pb, std::integral_constant<int, 0>{});
+                if (kt + 1 < nk) tile_steps(kt + 1, pb2, pb, pb1, pb2, std::integral_constant<int, 1>{});
             } else {
-                for (int kt = 0; kt < nk; ++kt) tile_steps(kt, pb, pb1, pb1, pb);
+                for (int kt = 0; kt < nk; ++kt) tile_steps(kt, pb, pb1, pb1, pb, std::integral_constant<int, 0>{});
             }
         } else {
 #pragma unroll
@@ -710,6 +800,7 @@ __device__ __forceinline__ void gemm_body(const GemmP& p, const unsigned bid, co
     }
     }   // exact / split loop
     DC_STAMP(2);
+    if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // no piece may land on the staging below
     __syncthreads();                  // (the staging below reuses the operand buffers)
 
     // ---- statistics epilogue (rows beyond M hold zeros and add nothing)
@@ -881,16 +972,16 @@ __device__ __forceinline__ void gemm_body(const GemmP& p, const unsigned bid, co
 #endif
 }
 
-template <int BM, int BN, int AL, int BL, int MODE, int EPI, int PRO = 0, int X3 = 0, int BP = 0>
+template <int BM, int BN, int AL, int BL, int MODE, int EPI, int PRO = 0, int X3 = 0, int BP = 0, int DMA = 0>
 __global__ __launch_bounds__(NT, 2) void gemm_kernel(GemmP p) {
-    gemm_body<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP>(p, blockIdx.x, gridDim.x);
+    gemm_body<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA>(p, blockIdx.x, gridDim.x);
 }
 // Two products of the SAME instantiation in one launch (round 6: the max-aggregation stream's and the s_mlp's last products of a
 // DeltaConv layer are independent): the first nb0 workgroups multiply p0, the rest p1 -- the body is the single kernel's.
-template <int BM, int BN, int AL, int BL, int MODE, int EPI, int PRO = 0, int X3 = 0, int BP = 0>
+template <int BM, int BN, int AL, int BL, int MODE, int EPI, int PRO = 0, int X3 = 0, int BP = 0, int DMA = 0>
 __global__ __launch_bounds__(NT, 2) void gemm_pair_kernel(GemmP p0, GemmP p1, unsigned nb0) {
-    if (blockIdx.x < nb0) gemm_body<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP>(p0, blockIdx.x, nb0);
-    else gemm_body<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP>(p1, blockIdx.x - nb0, gridDim.x - nb0);
+    if (blockIdx.x < nb0) gemm_body<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA>(p0, blockIdx.x, nb0);
+    else gemm_body<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA>(p1, blockIdx.x - nb0, gridDim.x - nb0);
 }
 
 struct Tile { int bm, bn; };
@@ -930,29 +1021,29 @@ struct GemmPending { GemmP p; unsigned blocks; size_t lds; GemmSingleFn single; 
 static thread_local GemmPending g_gemm_q[DC_FIN_MAX];
 static thread_local int g_gemm_n = 0;
 
-template <int BM, int BN, int AL, int BL, int MODE, int EPI, int PRO, int X3, int BP>
+template <int BM, int BN, int AL, int BL, int MODE, int EPI, int PRO, int X3, int BP, int DMA>
 void gemm_single_thunk(const GemmP& p, unsigned blocks, size_t lds, hipStream_t s) {
-    hipLaunchKernelGGL((gemm_kernel<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP>), dim3(blocks, 1), dim3(NT), lds, s, p);
+    hipLaunchKernelGGL((gemm_kernel<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA>), dim3(blocks, 1), dim3(NT), lds, s, p);
 }
-template <int BM, int BN, int AL, int BL, int MODE, int EPI, int PRO, int X3, int BP>
+template <int BM, int BN, int AL, int BL, int MODE, int EPI, int PRO, int X3, int BP, int DMA>
 void gemm_pair_thunk(const GemmP& p0, const GemmP& p1, unsigned b0, unsigned b1, size_t lds, hipStream_t s) {
     static unsigned long long configured = 0;
-    if (!dc_ensure_lds(&configured, reinterpret_cast<const void*>(&gemm_pair_kernel<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP>), lds, "dense product pair")) {
+    if (!dc_ensure_lds(&configured, reinterpret_cast<const void*>(&gemm_pair_kernel<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA>), lds, "dense product pair")) {
         (void)dc_take_lds_failure();        // the single kernel's opt-in held when both were queued: one launch each instead
-        gemm_single_thunk<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP>(p0, b0, lds, s);
-        gemm_single_thunk<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP>(p1, b1, lds, s);
+        gemm_single_thunk<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA>(p0, b0, lds, s);
+        gemm_single_thunk<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA>(p1, b1, lds, s);
         return;
     }
     GemmP q1 = p1;
     q1.stagger = 0;                         // (the phase shift is a first-round device: the second product's workgroups come later)
-    hipLaunchKernelGGL((gemm_pair_kernel<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP>), dim3(b0 + b1, 1), dim3(NT), lds, s, p0, q1, b0);
+    hipLaunchKernelGGL((gemm_pair_kernel<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA>), dim3(b0 + b1, 1), dim3(NT), lds, s, p0, q1, b0);
 }
 
-template <int BM, int BN, int AL, int BL, int MODE, int EPI, int PRO, int X3, int BP = 0>
+template <int BM, int BN, int AL, int BL, int MODE, int EPI, int PRO, int X3, int BP = 0, int DMA = 0>
 void launch_one(const GemmP& p, long tiles_m, int slabs, hipStream_t s) {
     static unsigned long long configured = 0;
     const size_t lds = lds_bytes(BM, BN, AL, BL);
-    if (!dc_ensure_lds(&configured, reinterpret_cast<const void*>(&gemm_kernel<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP>), lds, "dense product")) return;
+    if (!dc_ensure_lds(&configured, reinterpret_cast<const void*>(&gemm_kernel<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA>), lds, "dense product")) return;
     // the pairable kind: forward product from the step's weight planes with the BatchNorm-statistics epilogue (whole tiles)
     constexpr bool PAIRABLE = EPI == EPI_COLSTATS && BP == 1 && MODE == 0 && PRO == 0 && AL == A_MK && BL == B_NK;
     if (dc_gemm_take_request()) {           // (always consumed, whatever the kind)
@@ -960,22 +1051,22 @@ void launch_one(const GemmP& p, long tiles_m, int slabs, hipStream_t s) {
             if (slabs == 1 && g_gemm_n < DC_FIN_MAX) {
                 GemmPending& e = g_gemm_q[g_gemm_n++];
                 e.p = p; e.blocks = (unsigned)(tiles_m * p.tiles_n); e.lds = lds;
-                e.single = &gemm_single_thunk<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP>;
-                e.pair = &gemm_pair_thunk<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP>;
+                e.single = &gemm_single_thunk<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA>;
+                e.pair = &gemm_pair_thunk<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA>;
                 return;
             }
         }
     }
-    hipLaunchKernelGGL((gemm_kernel<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP>),
+    hipLaunchKernelGGL((gemm_kernel<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA>),
                        dim3((unsigned)(tiles_m * p.tiles_n), (unsigned)slabs), dim3(NT), lds, s, p);
 }
 
-template <int AL, int BL, int MODE, int EPI, int PRO, int X3 = 0, int BP = 0>
+template <int AL, int BL, int MODE, int EPI, int PRO, int X3 = 0, int BP = 0, int DMA = 0>
 void launch_tile(const GemmP& p, Tile t, long tiles_m, int slabs, hipStream_t s) {
-    if (t.bm == 128 && t.bn == 128) launch_one<128, 128, AL, BL, MODE, EPI, PRO, X3, BP>(p, tiles_m, slabs, s);
-    else if (t.bm == 128) launch_one<128, 64, AL, BL, MODE, EPI, PRO, X3, BP>(p, tiles_m, slabs, s);
-    else if (t.bn == 128) launch_one<64, 128, AL, BL, MODE, EPI, PRO, X3, BP>(p, tiles_m, slabs, s);
-    else launch_one<64, 64, AL, BL, MODE, EPI, PRO, X3, BP>(p, tiles_m, slabs, s);
+    if (t.bm == 128 && t.bn == 128) launch_one<128, 128, AL, BL, MODE, EPI, PRO, X3, BP, DMA>(p, tiles_m, slabs, s);
+    else if (t.bm == 128) launch_one<128, 64, AL, BL, MODE, EPI, PRO, X3, BP, DMA>(p, tiles_m, slabs, s);
+    else if (t.bn == 128) launch_one<64, 128, AL, BL, MODE, EPI, PRO, X3, BP, DMA>(p, tiles_m, slabs, s);
+    else launch_one<64, 64, AL, BL, MODE, EPI, PRO, X3, BP, DMA>(p, tiles_m, slabs, s);
 }
 
 // The unguarded path (whole tiles: every hot shape of the reference models) multiplies through the split products where
@@ -993,6 +1084,14 @@ void launch_fast(const GemmP& p, Tile t, long tiles_m, int slabs, int mode, hipS
     // simple loop: their registers).
     if constexpr (AL == A_MK && BL == B_NK) {
         if (p.Bp && mode == 0 && dc_option(DC_OPT_GEMM_EXACT) == 0) {
+            // plain products: the activation tiles reach LDS by LDS-DMA into a ring of three buffers (mode 0 already holds the A
+            // base and row stride to 16 bytes); switch DC_OPT_GEMM_A_REGS = 1: through staging registers as before (A/B, same bits)
+            if constexpr (PRO == 0) {
+                if (dc_option(DC_OPT_GEMM_A_REGS) == 0) {
+                    launch_tile<AL, BL, 0, EPI, PRO, 2, 1, 1>(p, t, tiles_m, slabs, s);
+                    return;
+                }
+            }
             launch_tile<AL, BL, 0, EPI, PRO, 2, 1>(p, t, tiles_m, slabs, s);
             return;
         }

@@ -50,7 +50,10 @@ const char* dc_last_error(void);
  * 11: value 1 = dense products with fewer than 256 workgroups keep 128-column tiles (round-6 rule off);
  * 12: weight gradients on whole tiles: 0 = the plane-image kernel (operands cut into bf16 planes once, at the LDS store) on the
  * launches it runs faster (128-row tiles, more than one workgroup per CU), 1 = the fp32-tile kernel everywhere (fallback, A/B partner), 2 = the plane-image kernel on every
- * whole tile (lab). */
+ * whole tile (lab);
+ * 13: plain dense products over pre-split weight planes (forward, input gradient, the statistics epilogues, the paired launch):
+ * 0 = the fp32 activation tiles reach LDS by 16-byte LDS-DMA into a ring of three buffers, 1 = through staging registers and
+ * ds_write_b128 into two padded buffers (the earlier loop: fallback, A/B partner).  Same floats into the same MFMAs: same bits. */
 int dc_set_option(int32_t key, int32_t value);
 
 /* Deferred finalisers (round 6): a column reduction is two launches (partials, finaliser).  Between dc_finalisers_begin() and
