@@ -14,3 +14,4 @@ from .pool import *               # noqa: F401,F403
 from .pool_vectors import *       # noqa: F401,F403
 from .resample import CloudPair, fps_levels, prefix_levels    # noqa: F401
 from .voxel import voxel_subsample                   # noqa: F401
+from .cluster import *            # noqa: F401,F403

@@ -47,7 +47,8 @@ def voxel_subsample(pos, size, ptr=None, batch=None, ptr_info=None, origin=None,
     row), ``"first"`` the member with the lowest row.
     -> ``(rows int64 [N_out], optr int64 [B+1], cluster int64 [N])``: ``rows[optr[b]:optr[b+1]]`` are cloud b's representatives
     as rows of ``pos``, ASCENDING (a stable subset: file order survives); ``cluster[i]`` is the output row of point i's cell, so
-    ``rows[cluster[i]]`` is i's representative and ``cluster`` indexes a pooled ``[N_out, C]`` tensor directly.  A point with a
+    ``rows[cluster[i]]`` is i's representative and ``cluster`` indexes a pooled ``[N_out, C]`` tensor directly
+    (``cluster_pool(x, cluster, len(rows), ...)`` pools onto it, ``cluster_unpool`` brings rows back).  A point with a
     non-finite coordinate, or outside every cloud of ``ptr``, belongs to no cell, is never picked and gets cluster -1.
 
     The rules (csrc/voxel_math.h; tests/voxel_restate.py restates them in numpy, bit for bit): per axis the cell is

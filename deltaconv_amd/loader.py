@@ -322,7 +322,7 @@ class DeviceDataset:
         return DeviceDataset(take(self.pos), ptr, np.full(s, m, dtype=np.int64), take(self.norm), take(self.x), take(self.y_point),
                              self.y_cloud, self.category)
 
-    def voxel_subsample(self, size, origin=None, pick="centre"):
+    def voxel_subsample(self, size, origin=None, pick="centre", reduce=None, num_classes=None):
         """A new store that keeps of every cloud one point per occupied grid cell of edge ``size`` (``geometry.voxel_subsample``:
         the member nearest the cell centre, or with ``pick="first"`` the first one; ``origin=None``: every cloud's grid starts at
         its own minimum, so a cloud thins the same way in any store).  ``pos``, ``norm``, ``x`` and per-point ``y`` are gathered by
@@ -330,13 +330,40 @@ class DeviceDataset:
         output offsets.  Two more attributes: ``source_rows`` (int64 [N_out]: the kept rows of THIS store) and ``cluster`` (int64
         [N]: for every row of this store the row of the new one that stands for it, -1 for a row with a non-finite coordinate) --
         ``Propagator(sub, parent)`` interpolates predictions back, ``cluster`` pools onto the thinned store.  Linear in the
-        points: it evens out a scan or an over-tessellated mesh before ``geodesic_subsample``.  Two device reads: the call's own and the output offsets."""
+        points: it evens out a scan or an over-tessellated mesh before ``geodesic_subsample``.  Two device reads: the call's own and the output offsets.
+
+        ``reduce=None`` (the default): every attribute is the representative's.  ``reduce="mean"``: the attributes are pooled over
+        the cells instead (``geometry.cluster_lists`` once, then one launch each) -- ``pos`` the cell barycentre and ``norm`` the
+        normalised mean normal (``cluster_mean_pos``: fp64 sums in row order; a cell whose normals cancel keeps its representative's
+        normal), ``x`` the fp32 mean (``cluster_pool_rows``), ``y_point`` the majority label (``cluster_majority``, ties to the
+        lowest label; ``num_classes``: the number of labels, read once from the store's labels -- one more device read -- where not
+        given).  ``source_rows``, ``cluster`` and the row order are the same in both modes."""
         from .geometry.voxel import voxel_subsample
+        if reduce not in (None, "mean"):
+            raise ValueError(f"voxel_subsample: reduce must be None or 'mean', got {reduce!r}")
         rows, optr, cluster = voxel_subsample(self.pos, size, ptr=self.ptr, origin=origin, pick=pick)
         take = lambda t: None if t is None else t[rows].contiguous()
         optr_host = optr.cpu().numpy()
-        sub = DeviceDataset(take(self.pos), optr, optr_host[1:] - optr_host[:-1], take(self.norm), take(self.x), take(self.y_point),
-                            self.y_cloud, self.category)
+        if reduce is None:
+            sub = DeviceDataset(take(self.pos), optr, optr_host[1:] - optr_host[:-1], take(self.norm), take(self.x),
+                                take(self.y_point), self.y_cloud, self.category)
+        else:
+            from .geometry.cluster import MAX_CLASSES, cluster_lists, cluster_majority, cluster_mean_pos, cluster_pool_rows
+            cptr, members = cluster_lists(cluster, int(rows.numel()))
+            norm = x = y_point = None
+            if self.norm is not None:
+                norm = cluster_mean_pos(self.norm, cptr, members, normalize=True)
+                norm = torch.where((norm == 0).all(1, keepdim=True), take(self.norm), norm)
+            if self.x is not None:
+                x = cluster_pool_rows(self.x, cptr, members, "mean")[0]
+            if self.y_point is not None:
+                if num_classes is None:
+                    num_classes = max(int(self.y_point.max()) + 1, 1) if self.y_point.numel() else 1
+                if not 1 <= int(num_classes) <= MAX_CLASSES:
+                    raise ValueError(f"voxel_subsample: num_classes = {int(num_classes)} outside [1, {MAX_CLASSES}]")
+                y_point = cluster_majority(self.y_point, cptr, members, int(num_classes))
+            sub = DeviceDataset(cluster_mean_pos(self.pos, cptr, members), optr, optr_host[1:] - optr_host[:-1], norm, x, y_point,
+                                self.y_cloud, self.category)
         sub.source_rows, sub.cluster = rows, cluster
         return sub
 

@@ -60,7 +60,7 @@ def prepare(items, dev, args):
     if args.vertex_clouds:
         cloud = meshes.vertex_cloud()
         if args.voxel_size is not None:                 # one vertex per grid cell first: linear, and it evens out the tessellation
-            cloud = cloud.voxel_subsample(args.voxel_size)
+            cloud = cloud.voxel_subsample(args.voxel_size, reduce=args.voxel_reduce)
         return cloud.geodesic_subsample(args.num_points, seed=args.seed, large="device" if args.device_fps_large else "host")
     return meshes.sample_points(args.num_points * args.sampling_margin, include_normals=True, include_labels=True,
                                 seed=args.seed).geodesic_subsample(args.num_points, seed=args.seed)
@@ -84,6 +84,9 @@ def main(argv=None):
     ap.add_argument("--voxel-size", type=float, default=None,
                     help="with --vertex-clouds: thin every vertex cloud to one vertex per grid cell of this edge length "
                          "(DeviceDataset.voxel_subsample; the meshes are normalised to about unit extent) before the geodesic sampling")
+    ap.add_argument("--voxel-reduce", choices=["mean"], default=None,
+                    help="with --voxel-size: 'mean' pools every cell's attributes (barycentre, mean normal, majority label) instead "
+                         "of keeping its representative's (DeviceDataset.voxel_subsample(reduce='mean'))")
     ap.add_argument("--layers", type=int, default=8, help="convolution layers (train_shapeseg.py:71: 8)")
     ap.add_argument("--channels", type=int, default=128, help="channels of every layer (train_shapeseg.py:71: 128)")
     ap.add_argument("--seed", type=int, default=1, help="of the split, the surface samples, the FPS starts and the loader")
@@ -98,6 +101,8 @@ def main(argv=None):
         raise SystemExit("--device-fps-large samples the vertex clouds of --vertex-clouds: it needs --vertex-clouds")
     if args.voxel_size is not None and not args.vertex_clouds:
         raise SystemExit("--voxel-size thins the vertex clouds of --vertex-clouds: it needs --vertex-clouds")
+    if args.voxel_reduce is not None and args.voxel_size is None:
+        raise SystemExit("--voxel-reduce pools the cells of --voxel-size: it needs --voxel-size")
 
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)

@@ -890,6 +890,64 @@ int dc_voxel_subsample(const float* pos, const int64_t* ptr, int32_t B, int64_t 
                        float size_z, const float* origin, int32_t pick, int64_t* rows, int64_t* optr, int64_t* cluster,
                        int64_t* info, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- pooling over the cells of a cluster vector (csrc/cluster.hip, csrc/cluster_math.h) ----------------------------------------- */
+/* The workspace of one dc_cluster_lists call: counters / fill cursors [num_cells], the scan's block sums and the unordered fill
+ * [num_points], 8 bytes each -- linear.  0: a negative size, or more than 2^31 - 1 points or cells. */
+size_t dc_cluster_lists_workspace_bytes(int64_t num_points, int64_t num_cells);
+/* The member lists of a cluster vector -- the CSR form of torch_scatter's index: row i belongs to cell cluster[i] iff
+ * 0 <= cluster[i] < num_cells; any other value (-1: dc_voxel_subsample's "no cell") belongs to none.
+ *   cluster     DEVICE int64 [num_points]: dc_voxel_subsample's, or the caller's
+ *   cptr        DEVICE int64 [num_cells + 1]: cell j's rows are members[cptr[j] .. cptr[j+1]); cptr[num_cells] = the rows with a cell
+ *   members     DEVICE int64 [num_points]: the rows of every cell in ASCENDING order; entries from cptr[num_cells] on are -1
+ *   workspace   DEVICE, 8-byte aligned, workspace_bytes >= dc_cluster_lists_workspace_bytes(num_points, num_cells)
+ * Count (integer atomics), scan (list_scan.h), unordered fill, then a ranking pass with one thread per fill position: six launches
+ * whose sizes depend on num_points and num_cells alone, stream-ordered, no allocation, no synchronisation -- capturable, and a
+ * captured call replays on a cluster vector written in place.  Only the place of a row in the unordered fill depends on the race,
+ * and the ranks do not: the same bits on every run.  The ranking is QUADRATIC in a list's length (a cell that holds all 262 144
+ * rows of a call: 262 144 compares per thread -- slow, not a hang).  Sizes out of range, a null pointer, a workspace that is
+ * missing, misaligned or too small: DC_ERR_ARG with a message. */
+int dc_cluster_lists(const int64_t* cluster, int64_t num_points, int64_t num_cells, int64_t* cptr, int64_t* members,
+                     void* workspace, size_t workspace_bytes, void* stream);
+/* torch_scatter.scatter(x, cluster, reduce = "max" | "min" | "sum" | "mean") / torch_geometric's max_pool, avg_pool_x over the lists
+ * of dc_cluster_lists, by the rules of csrc/cluster_math.h: the members of a cell in ascending row order, the first copied bit for
+ * bit, a later one taken iff strictly larger / smaller (ties keep the lower row, a later NaN is never taken, a first NaN stays) or
+ * added with every addition rounded on its own; the mean divides once by the member count; an empty cell gives zeros.
+ *   x           DEVICE [num_points, C] fp32, rows ldx >= C apart; C >= 1 (16-byte loads where x, ldx and C allow, scalar otherwise)
+ *   mode        0 max, 1 min, 2 sum, 3 mean (the codes of dc_seg_reduce)
+ *   out         DEVICE [num_cells, C] fp32, rows ldo apart: every row is written
+ *   arg         DEVICE int32 [num_cells, C], rows ldarg apart (max / min; may be NULL for sum / mean, which do not write it): the ROW
+ *               of x every channel came from, -1 for an empty cell
+ * num_points and num_cells below 2^31, else DC_ERR_ARG (as a bad mode, a leading dimension below C, a null pointer).  One thread
+ * per (cell, group of 4 channels), one launch, no atomics, no synchronisation: a function of the inputs only. */
+int dc_cluster_pool(const float* x, int64_t ldx, int64_t num_points, int32_t C, const int64_t* cptr, const int64_t* members,
+                    int64_t num_cells, int32_t mode, float* out, int64_t ldo, int32_t* arg, int64_t ldarg, void* stream);
+/* The gradient of dc_cluster_pool w.r.t. x: every point belongs to one cell, so it is a gather -- one thread per (point, group of 4
+ * channels).  max / min: dx[i,c] = arg[cl,c] == i ? g[cl,c] : 0; sum: g[cl,c]; mean: g[cl,c] / (float)(cptr[cl+1] - cptr[cl]), the
+ * quotient rounded on its own (as dc_knn_pool_backward's term); a point without a cell gets zeros.  Every row of dx is written.
+ *   g           DEVICE [num_cells, C] fp32, rows ldg apart;  cluster  DEVICE int64 [num_points]
+ *   cptr        DEVICE int64 [num_cells + 1], read by the mean only (may be NULL otherwise)
+ *   arg, ldarg  what dc_cluster_pool wrote; may be NULL for sum / mean
+ *   dx          DEVICE [num_points, C] fp32, rows ldx apart
+ * The checks of dc_cluster_pool: DC_ERR_ARG.  One launch, no atomics, no synchronisation. */
+int dc_cluster_pool_backward(const float* g, int64_t ldg, int64_t num_cells, int32_t C, const int64_t* cluster, int64_t num_points,
+                             const int64_t* cptr, const int32_t* arg, int64_t ldarg, int32_t mode, float* dx, int64_t ldx,
+                             void* stream);
+/* The un-pooling out[i] = x[cluster[i]] (zeros for a point without a cell): x [num_cells, C] -> out [num_points, C].  Its gradient
+ * w.r.t. x is dc_cluster_pool in sum mode over the lists: the ordered, atomics-free index_add_.  One launch. */
+int dc_cluster_gather(const float* x, int64_t ldx, int64_t num_cells, int32_t C, const int64_t* cluster, int64_t num_points,
+                      float* out, int64_t ldo, void* stream);
+/* torch_geometric's pool_pos, held to fp64: per cell the sum of its [num_points,3] fp32 rows in member order in fp64, ONE fp64
+ * division by the count and ONE rounding to fp32 (an fp32 chain loses the low bits of a cloud shifted by 4 096).  normalize = 1
+ * (normals): the fp64 sum divided by its fp64 norm instead, zeros where that norm is zero or not finite.  An empty cell gives zeros.
+ *   p  DEVICE [num_points,3] contiguous fp32;  out  DEVICE [num_cells,3] contiguous fp32.  One thread per cell, one launch. */
+int dc_cluster_mean3(const float* p, int64_t num_points, const int64_t* cptr, const int64_t* members, int64_t num_cells,
+                     int32_t normalize, float* out, void* stream);
+/* Per cell the label with the most members, ties to the lowest label; labels outside [0, num_classes) are ignored; a cell without
+ * a valid label gets -1.  Integer counting only: per cell the classes between its smallest and largest label times its members.
+ *   labels  DEVICE int64 [num_points];  num_classes in [1, 1024], else DC_ERR_ARG;  out  DEVICE int64 [num_cells].  One launch. */
+int dc_cluster_majority(const int64_t* labels, int64_t num_points, const int64_t* cptr, const int64_t* members, int64_t num_cells,
+                        int32_t num_classes, int64_t* out, void* stream);
+
 /* ---- surface sampling of a batch of triangle meshes (csrc/mesh.hip, csrc/mesh_math.h) ------------------------------------------ */
 /* Bytes of workspace dc_mesh_sample needs for meshes of F_total faces in all: the cdf, 8 bytes per face.  Reference:
  * deltaconv/transforms/sample_points.py:22-59 (the area vector of :29-32 is the only state between its stages). */
