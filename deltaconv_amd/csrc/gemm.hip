@@ -49,6 +49,7 @@
 // cycles) against 32 KB of global loads (8 B/clk/CU) and 16 ds_read_b128 per wave.  Split products: 48 bf16 MFMAs per wave
 // (1536 cycles of a 2.5 PFLOP/s pipe that runs power-limited at ~1.65 GHz) + 288 split instructions on the VALU.
 #include <algorithm>
+#include <cstdlib>
 #include <type_traits>
 #include "common.h"
 #include "nn_math.h"
@@ -142,7 +143,7 @@ __device__ __forceinline__ void split8(const f32x4 a, const f32x4 b, Planes& o) 
     }
 }
 template <int BM, int BN, int AL, int BL, int MODE, int EPI, int PRO = 0, int X3 = 0, int BP = 0, int DMA = 0>
-__device__ __forceinline__ void gemm_body(const GemmP& p, const unsigned bid, const unsigned gemm_blocks) {
+__device__ __forceinline__ void gemm_body(const GemmP& p, const unsigned bid, const unsigned gemm_blocks, const unsigned slab) {
     static_assert(!BP || (X3 == 2 && AL == A_MK && BL == B_NK && MODE == 0), "pre-split B planes: pipelined split loop, K-contiguous operands, whole tiles");
     static_assert(!DMA || (BP && !PRO), "LDS-DMA activation ring: plain products over pre-split weight planes only");
     constexpr bool FAST = MODE == 0;               // no guards anywhere (loads, statistics, stores)
@@ -171,7 +172,7 @@ __device__ __forceinline__ void gemm_body(const GemmP& p, const unsigned bid, co
     // workgroup placed on the CU) by about half a K loop in the first round puts one workgroup's epilogue under the
     // other's K loop for the rest of the launch.
     DC_STAMP(0);
-    if (p.stagger > 0 && (long)blockIdx.y * gemm_blocks + bid < p.resident) {
+    if (p.stagger > 0 && (long)slab * gemm_blocks + bid < p.resident) {
         const unsigned slot = __builtin_amdgcn_s_getreg((3 << 11) | 4);      // HW_REG_HW_ID bits [3:0]
         if (slot & 1) {
             const unsigned long long t0 = __builtin_amdgcn_s_memtime();
@@ -183,7 +184,7 @@ __device__ __forceinline__ void gemm_body(const GemmP& p, const unsigned bid, co
         const long q = gemm_blocks >> 3, r = gemm_blocks & 7, xcd = blk & 7, idx = blk >> 3;
         blk = xcd * q + (xcd < r ? xcd : r) + idx;
     }
-    const long kbeg = (long)blockIdx.y * p.k_per_slab;
+    const long kbeg = (long)slab * p.k_per_slab;
     const long kend = min(p.K, kbeg + p.k_per_slab);
     const long tm = blk / p.tiles_n;
     const int tn = (int)(blk - tm * p.tiles_n);
@@ -876,7 +877,7 @@ __device__ __forceinline__ void gemm_body(const GemmP& p, const unsigned bid, co
             for (int q = 0; q < 16; ++q)
                 stg[(i * 32 + (q & 3) + 8 * (q >> 2) + 4 * lh) * WN + jn * 32 + li] = acc[i][jn][q];
     __syncthreads();
-    float* cbase = p.C + (long)blockIdx.y * p.slab_stride;
+    float* cbase = p.C + (long)slab * p.slab_stride;
     if (EPI == EPI_VNSTATS && p.store_y) {
         // Combined store (first block of a VectorMLP): C = y[M, N/2], (y_u, y_v) = vn_combine of the staged (P, Q) pairs --
         // the same subtract / add of the same floats as dc_vn_* (combine = 2) apply to a stored PQ, so the same bits.  A lane
@@ -974,14 +975,36 @@ __device__ __forceinline__ void gemm_body(const GemmP& p, const unsigned bid, co
 
 template <int BM, int BN, int AL, int BL, int MODE, int EPI, int PRO = 0, int X3 = 0, int BP = 0, int DMA = 0>
 __global__ __launch_bounds__(NT, 2) void gemm_kernel(GemmP p) {
-    gemm_body<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA>(p, blockIdx.x, gridDim.x);
+    gemm_body<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA>(p, blockIdx.x, gridDim.x, blockIdx.y);
 }
 // Two products of the SAME instantiation in one launch (round 6: the max-aggregation stream's and the s_mlp's last products of a
 // DeltaConv layer are independent): the first nb0 workgroups multiply p0, the rest p1 -- the body is the single kernel's.
 template <int BM, int BN, int AL, int BL, int MODE, int EPI, int PRO = 0, int X3 = 0, int BP = 0, int DMA = 0>
 __global__ __launch_bounds__(NT, 2) void gemm_pair_kernel(GemmP p0, GemmP p1, unsigned nb0) {
-    if (blockIdx.x < nb0) gemm_body<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA>(p0, blockIdx.x, nb0);
-    else gemm_body<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA>(p1, blockIdx.x - nb0, gridDim.x - nb0);
+    if (blockIdx.x < nb0) gemm_body<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA>(p0, blockIdx.x, nb0, blockIdx.y);
+    else gemm_body<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA>(p1, blockIdx.x - nb0, gridDim.x - nb0, blockIdx.y);
+}
+// A block's weight gradient and input gradient in ONE launch (1-D grid): dW = dh^T X and dX = dh W read the same dy (and h +
+// coefficients in the prologue form), write disjoint outputs and do not depend on each other.  The first nb_a = tiles_a x slabs
+// workgroups run the weight-gradient body of instantiation IA -- slab-major like its own dim3(tiles, slabs) grid -- the rest the
+// input-gradient body of IB.  The long, barrier-heavy weight-gradient workgroups come first: every CU gets one of them before the
+// input-gradient workgroups fill its second slot (alone, a 2 tiles x 128 slabs launch leaves that slot empty; the 64 x 64 plans
+// with ~768 workgroups leave a ragged last round).  Same bodies on the same data in the same order: same bits as the two launches.
+template <int BM_, int BN_, int AL_, int BL_, int MODE_, int EPI_, int PRO_, int X3_, int BP_, int DMA_>
+struct Inst {
+    static __device__ __forceinline__ void run(const GemmP& p, unsigned bid, unsigned blocks, unsigned slab) {
+        gemm_body<BM_, BN_, AL_, BL_, MODE_, EPI_, PRO_, X3_, BP_, DMA_>(p, bid, blocks, slab);
+    }
+    static const void* kernel() { return reinterpret_cast<const void*>(&gemm_kernel<BM_, BN_, AL_, BL_, MODE_, EPI_, PRO_, X3_, BP_, DMA_>); }
+};
+template <class IA, class IB>
+__global__ __launch_bounds__(NT, 2) void gemm_dual_kernel(GemmP pa, GemmP pb, unsigned nb_a, unsigned tiles_a) {
+    if (blockIdx.x < nb_a) {
+        const unsigned slab = blockIdx.x / tiles_a;
+        IA::run(pa, blockIdx.x - slab * tiles_a, tiles_a, slab);
+    } else {
+        IB::run(pb, blockIdx.x - nb_a, gridDim.x - nb_a, 0);
+    }
 }
 
 struct Tile { int bm, bn; };
@@ -1039,6 +1062,12 @@ void gemm_pair_thunk(const GemmP& p0, const GemmP& p1, unsigned b0, unsigned b1,
     hipLaunchKernelGGL((gemm_pair_kernel<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA>), dim3(b0 + b1, 1), dim3(NT), lds, s, p0, q1, b0);
 }
 
+// ---- resolution without a launch: while g_resolve points at a record, the product that run_gemm / dc_tn_lds_launch resolve (tile,
+// load mode, multiply path, plan, plane hint: all by the code every call runs) is written there instead of being launched --
+// {parameters, tiles, slabs, LDS, instantiation}.  dc_gemm_both_launch below pairs two such records or launches them one by one.
+struct GemmResolved { GemmP p; unsigned blocks, slabs; size_t lds; const void* kernel; int inst[10]; };  // kernel = &gemm_kernel<inst>
+static thread_local GemmResolved* g_resolve = nullptr;
+
 template <int BM, int BN, int AL, int BL, int MODE, int EPI, int PRO, int X3, int BP = 0, int DMA = 0>
 void launch_one(const GemmP& p, long tiles_m, int slabs, hipStream_t s) {
     static unsigned long long configured = 0;
@@ -1056,6 +1085,12 @@ void launch_one(const GemmP& p, long tiles_m, int slabs, hipStream_t s) {
                 return;
             }
         }
+    }
+    if (g_resolve) {
+        *g_resolve = GemmResolved{p, (unsigned)(tiles_m * p.tiles_n), (unsigned)slabs, lds,
+                                  reinterpret_cast<const void*>(&gemm_kernel<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA>),
+                                  {BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA}};
+        return;
     }
     hipLaunchKernelGGL((gemm_kernel<BM, BN, AL, BL, MODE, EPI, PRO, X3, BP, DMA>),
                        dim3((unsigned)(tiles_m * p.tiles_n), (unsigned)slabs), dim3(NT), lds, s, p);
@@ -1310,6 +1345,100 @@ int dc_tn_lds_launch(const float* A, long lda, const float* B, long ldb, long R,
     if (h) launch_fast<A_KM, B_KN, EPI_NONE, 1>(p, t, tiles_m, pl.slabs, mode, s);
     else launch_fast<A_KM, B_KN, EPI_NONE>(p, t, tiles_m, pl.slabs, mode, s);
     return pl.slabs;
+}
+
+// ---- a block's two gradient products, one launch where the table has the pair (called from gemm_tn.hip: dc_linear_*backward_both) ----
+namespace {
+typedef bool (*GemmDualFn)(const GemmResolved&, const GemmResolved&, hipStream_t);
+template <class IA, class IB>
+bool gemm_dual_thunk(const GemmResolved& a, const GemmResolved& b, hipStream_t s) {
+    static unsigned long long configured = 0;
+    const size_t lds = std::max(a.lds, b.lds);              // (a function of the two instantiations only)
+    if (!dc_ensure_lds(&configured, reinterpret_cast<const void*>(&gemm_dual_kernel<IA, IB>), lds, "dense product pair (dW, dX)")) {
+        (void)dc_take_lds_failure();        // each kernel's own opt-in held when the products were resolved: one launch each instead
+        return false;
+    }
+    GemmP qb = b.p;
+    qb.stagger = 0;                         // (a first-round device: the second product's workgroups come later, as in gemm_pair_thunk)
+    hipLaunchKernelGGL((gemm_dual_kernel<IA, IB>), dim3(a.blocks * a.slabs + b.blocks), dim3(NT), lds, s, a.p, qb, a.blocks * a.slabs,
+                       a.blocks);
+    return true;
+}
+void launch_resolved(const GemmResolved& r, hipStream_t s) {
+    GemmP p = r.p;
+    void* args[] = {&p};
+    (void)hipLaunchKernel(r.kernel, dim3(r.blocks, r.slabs), dim3(NT), args, r.lds, s);      // (errors: the caller's DC_CHECK_LAUNCH)
+}
+// The pairs that run as one launch: those of the C2 training step's backward on whole tiles that measured faster inside the step
+// (profiles/gemm_dual_ab.txt: -2.4 ... -7.1 us each, 207 -> 181 us over five launches).  Left as two launches: TnPro128 + DxPro128
+// (51.32 -> 51.28 us: both launches already fill the device), the guarded forms, and the further pairs of the C3 - C5 steps, listed
+// in that file and not measured yet.  DC_GEMM_DUAL_DEBUG=1 prints every pair a process meets, once, with what became of it.
+//                    BM   BN  AL BL MODE EPI PRO X3 BP DMA
+using TnPro128 = Inst<128, 128, 1, 1, 0, 0, 1, 1, 0, 0>;     // weight gradient, prologue form, 128 x 128 tiles that gemm_kernel keeps
+using TnPro64  = Inst<64, 64, 1, 1, 0, 0, 1, 0, 0, 0>;       // ... 64 x 64 tiles (small plans), exact chain
+using TnPlain64 = Inst<64, 64, 1, 1, 0, 0, 0, 0, 0, 0>;      // ... plain form
+using DxPro128 = Inst<128, 128, 0, 0, 0, 0, 1, 2, 1, 0>;     // input gradient over W^T's planes, prologue form
+using DxPro64x128 = Inst<64, 128, 0, 0, 0, 0, 1, 2, 1, 0>;
+using DxPro64 = Inst<64, 64, 0, 0, 0, 0, 1, 2, 1, 0>;
+using DxPlain128x64 = Inst<128, 64, 0, 0, 0, 0, 0, 2, 1, 1>; // plain form: activation tiles by LDS-DMA
+struct GemmDualEntry { const void* ka; const void* kb; GemmDualFn fn; };
+template <class IA, class IB> GemmDualEntry dual_entry() { return {IA::kernel(), IB::kernel(), &gemm_dual_thunk<IA, IB>}; }
+GemmDualFn find_dual(const GemmResolved& a, const GemmResolved& b) {
+    static const GemmDualEntry table[] = {
+        dual_entry<TnPro128, DxPro64x128>(), dual_entry<TnPro64, DxPro64>(), dual_entry<TnPro64, DxPro128>(),
+        dual_entry<TnPlain64, DxPlain128x64>(),
+    };
+    for (const GemmDualEntry& e : table)
+        if (e.ka == a.kernel && e.kb == b.kernel) return e.fn;
+    return nullptr;
+}
+void dual_debug(const GemmResolved& a, const GemmResolved& b, bool paired) {
+    static const bool on = [] { const char* e = getenv("DC_GEMM_DUAL_DEBUG"); return e && *e && *e != '0'; }();
+    if (!on) return;
+    static thread_local const void* seen[64][2];
+    static thread_local int n_seen = 0;
+    for (int i = 0; i < n_seen; ++i)
+        if (seen[i][0] == a.kernel && seen[i][1] == b.kernel) return;
+    if (n_seen < 64) { seen[n_seen][0] = a.kernel; seen[n_seen][1] = b.kernel; ++n_seen; }
+    auto tuple = [](const int (&v)[10], char* out) {
+        snprintf(out, 64, "<%d, %d, %d, %d, %d, %d, %d, %d, %d, %d>", v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9]);
+    };
+    char ta[64], tb[64];
+    tuple(a.inst, ta); tuple(b.inst, tb);
+    fprintf(stderr, "dc gemm dual: dW %s %u x %u workgroups, dX %s %u workgroups: %s\n", ta, a.blocks, a.slabs, tb, b.blocks,
+            paired ? "one launch" : "two launches");
+}
+}  // namespace
+
+// partial[slab][N][K] = the slab products of dW = dh^T X, and dX[R, K] (+)= dh W; dh = dy, or the BatchNorm-backward prologue of
+// (dy, h, coefs) when h is given.  -> DC_OK or an error code (message set); *slabs <- the number of partial tiles.
+int dc_gemm_both_launch(const char* name, const float* dy, long lddy, const float* h, long ldh, const float* coefs, float slope,
+                        const float* X, long ldx, const float* W, long ldw, long R, int N, int K, float* partial, float* dX,
+                        long lddx, int accumulate, int tile, int* slabs, hipStream_t s) {
+    const Prologue pro{h, ldh, coefs, N, slope};
+    const bool pairing = dc_option(DC_OPT_GEMM_NO_DUAL) == 0;
+    GemmResolved ra{}, rb{};
+    // the weight gradient resolves first: a launch at once where dc_tn_lds_launch sends it to the plane-image kernel (ra stays empty)
+    g_resolve = pairing ? &ra : nullptr;
+    *slabs = dc_tn_lds_launch(dy, lddy, X, ldx, R, N, K, partial, s, h, ldh, coefs, slope);
+    g_resolve = pairing && ra.kernel ? &rb : nullptr;
+    const int rc = run_gemm(name, B_KN, EPI_NONE, dy, lddy, W, ldw, R, K, N, dX, lddx, accumulate, tile, nullptr, 0, s, h ? &pro : nullptr);
+    g_resolve = nullptr;
+    if (ra.kernel) {
+        GemmDualFn dual = rc == DC_OK && rb.kernel ? find_dual(ra, rb) : nullptr;
+        if (rc == DC_OK && rb.kernel) dual_debug(ra, rb, dual != nullptr);
+        if (!dual || !dual(ra, rb, s)) {
+            launch_resolved(ra, s);
+            if (rc == DC_OK && rb.kernel) launch_resolved(rb, s);
+        }
+    }
+    if (rc != DC_OK) return rc;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        dc_set_error("%s: %s", name, hipGetErrorString(e));
+        return DC_ERR_LAUNCH;
+    }
+    return DC_OK;
 }
 
 // Y[M,N] (ldy) = X[M,K] (ldx) W[N,K]^T (ldw).  tile: 0 = automatic; 1..4 = 128x128, 128x64, 64x64, 64x128.

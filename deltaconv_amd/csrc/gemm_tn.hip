@@ -417,6 +417,84 @@ DC_EXPORT int dc_linear_bn_backward_weight_slabs(const float* dy, int64_t lddy, 
     return DC_OK;
 }
 
+// ---- both gradients of a block in one call: dW[N,K] (lddw) (+)= dh^T X and dX[R,K] (lddx) (+)= dh W, dh [R,N] = dy (plain form) or
+// the BatchNorm-backward prologue of (dy, h, coefs).  The two products are resolved exactly as by dc_gemm_tn /
+// dc_linear_bn_backward_weight and dc_linear_backward_input / dc_linear_bn_backward_input; where gemm.hip's table holds their pair of
+// instantiations they run as ONE launch (gemm_dual_kernel), else as the two launches of those calls -- the same bits either way.
+// Workspace: dc_gemm_tn_workspace_bytes(R, N, K).  *_slabs: the partial tiles only, for dc_gemm_tn_reduce_many.
+int dc_gemm_both_launch(const char* name, const float* dy, long lddy, const float* h, long ldh, const float* coefs, float slope,
+                        const float* X, long ldx, const float* W, long ldw, long R, int N, int K, float* partial, float* dX,
+                        long lddx, int accumulate, int tile, int* slabs, hipStream_t s);
+extern "C" int dc_linear_backward_input(const float* dY, int64_t lddy, const float* W, int64_t ldw, int64_t M, int32_t N, int32_t K,
+                                        float* dX, int64_t lddx, int32_t accumulate, int32_t tile, void* stream);      // gemm.hip
+namespace {
+int both_impl(const char* name, bool pro, const float* dy, int64_t lddy, const float* h, int64_t ldh, const float* coefs, float slope,
+              const float* X, int64_t ldx, const float* W, int64_t ldw, int64_t R, int32_t N, int32_t K, float* dW, int64_t lddw,
+              int32_t accumulate_w, float* dX, int64_t lddx, int32_t accumulate_x, int32_t tile, void* workspace,
+              size_t workspace_bytes, int32_t* slabs_out, void* stream) {
+    if (!(dy && X && W && dX && (slabs_out || dW) && (!pro || (h && coefs)))) {
+        dc_set_error("%s: null pointer", name);
+        return DC_ERR_ARG;
+    }
+    if (!(R >= 1 && N >= 1 && K >= 1 && lddy >= N && (!pro || ldh >= N) && ldx >= K && ldw >= K && lddx >= K && (slabs_out || lddw >= K))) {
+        dc_set_error("%s: bad size", name);
+        return DC_ERR_ARG;
+    }
+    if (!(lddy < (1 << 21) && ldh < (1 << 21) && ldx < (1 << 21) && ldw < (1 << 21))) {
+        dc_set_error("%s: leading dimension above 2^21 elements", name);
+        return DC_ERR_ARG;
+    }
+    if (!workspace || workspace_bytes < dc_gemm_tn_workspace_bytes(R, N, K)) {
+        dc_set_error("%s: workspace too small", name);
+        return DC_ERR_WORKSPACE;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float* partial = static_cast<float*>(workspace);
+    int slabs = 0;
+    if (int rc = dc_gemm_both_launch(name, dy, (long)lddy, pro ? h : nullptr, pro ? (long)ldh : 0, pro ? coefs : nullptr, slope, X,
+                                     (long)ldx, W, (long)ldw, (long)R, N, K, partial, dX, (long)lddx, accumulate_x, tile, &slabs, s))
+        return rc;
+    if (slabs_out) *slabs_out = slabs;
+    else launch_tn_reduce(partial, slabs, (long)N * K, K, dW, (long)lddw, accumulate_w, s);
+    DC_CHECK_LAUNCH(name);
+    return DC_OK;
+}
+}  // namespace
+
+DC_EXPORT int dc_linear_backward_both(const float* dY, int64_t lddy, const float* X, int64_t ldx, const float* W, int64_t ldw,
+                                      int64_t R, int32_t N, int32_t K, float* dW, int64_t lddw, int32_t accumulate_w, float* dX,
+                                      int64_t lddx, int32_t accumulate_x, int32_t tile, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+    if (dc_option(DC_OPT_TN_LDS) == 2) {    // (lab: the direct-load weight-gradient kernel of dc_gemm_tn -- the two calls as they are)
+        if (int rc = dc_gemm_tn(dY, lddy, X, ldx, R, N, K, dW, lddw, accumulate_w, workspace, workspace_bytes, stream)) return rc;
+        return dc_linear_backward_input(dY, lddy, W, ldw, R, N, K, dX, lddx, accumulate_x, tile, stream);
+    }
+    return both_impl("dc_linear_backward_both", false, dY, lddy, nullptr, 0, nullptr, 0.f, X, ldx, W, ldw, R, N, K, dW, lddw,
+                     accumulate_w, dX, lddx, accumulate_x, tile, workspace, workspace_bytes, nullptr, stream);
+}
+DC_EXPORT int dc_linear_backward_both_slabs(const float* dY, int64_t lddy, const float* X, int64_t ldx, const float* W, int64_t ldw,
+                                            int64_t R, int32_t N, int32_t K, float* dX, int64_t lddx, int32_t accumulate_x,
+                                            int32_t tile, void* workspace, size_t workspace_bytes, int32_t* slabs, void* stream) {
+    DC_REQUIRE(slabs, "dc_linear_backward_both_slabs: null pointer");
+    return both_impl("dc_linear_backward_both_slabs", false, dY, lddy, nullptr, 0, nullptr, 0.f, X, ldx, W, ldw, R, N, K, nullptr, 0,
+                     0, dX, lddx, accumulate_x, tile, workspace, workspace_bytes, slabs, stream);
+}
+DC_EXPORT int dc_linear_bn_backward_both(const float* dy, int64_t lddy, const float* h, int64_t ldh, const float* coefs, float slope,
+                                         const float* X, int64_t ldx, const float* W, int64_t ldw, int64_t R, int32_t N, int32_t K,
+                                         float* dW, int64_t lddw, int32_t accumulate_w, float* dX, int64_t lddx,
+                                         int32_t accumulate_x, int32_t tile, void* workspace, size_t workspace_bytes, void* stream) {
+    return both_impl("dc_linear_bn_backward_both", true, dy, lddy, h, ldh, coefs, slope, X, ldx, W, ldw, R, N, K, dW, lddw,
+                     accumulate_w, dX, lddx, accumulate_x, tile, workspace, workspace_bytes, nullptr, stream);
+}
+DC_EXPORT int dc_linear_bn_backward_both_slabs(const float* dy, int64_t lddy, const float* h, int64_t ldh, const float* coefs,
+                                               float slope, const float* X, int64_t ldx, const float* W, int64_t ldw, int64_t R,
+                                               int32_t N, int32_t K, float* dX, int64_t lddx, int32_t accumulate_x, int32_t tile,
+                                               void* workspace, size_t workspace_bytes, int32_t* slabs, void* stream) {
+    DC_REQUIRE(slabs, "dc_linear_bn_backward_both_slabs: null pointer");
+    return both_impl("dc_linear_bn_backward_both_slabs", true, dy, lddy, h, ldh, coefs, slope, X, ldx, W, ldw, R, N, K, nullptr, 0,
+                     0, dX, lddx, accumulate_x, tile, workspace, workspace_bytes, slabs, stream);
+}
+
 DC_EXPORT int dc_gemm_tn_reduce_many(const int64_t* partials, const int64_t* outs, const int64_t* ldc, const int32_t* rows,
                                      const int32_t* cols, const int32_t* slabs, const int32_t* accumulate, int32_t count,
                                      void* stream) {

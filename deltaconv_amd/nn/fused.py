@@ -866,10 +866,47 @@ def mm_nn(dy, w, out=None, accumulate=False):
     return out
 
 
+def _both_applies(dh, x, w, dx_out):
+    """linear_grads through ONE call (dc_linear_backward_both): fp32 device operands, at least one row, and a weight gradient
+    that fits one launch (gemm_tn's column-block loop stays with gemm_tn)."""
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 for t in (dh, x, w)):
+        return False
+    r, n = dh.shape
+    k = w.shape[1]
+    return r >= 1 and n >= 1 and k >= 1 and OWN_TN_MAX_OUTPUTS // n >= k
+
+
+def _linear_grads_both(dh, x, w, dx_out, accumulate):
+    """dW = dh^T x and dX = dh w from one entry point: the library runs the two products as one launch where it holds their
+    pair of kernels (csrc/gemm.hip: gemm_dual_kernel; option 14 = 1: never), else as the launches gemm_tn + mm_nn make."""
+    r, n = dh.shape
+    k = w.shape[1]
+    dev = dh.device
+    dw = torch.empty(n, k, dtype=torch.float32, device=dev)
+    if dx_out is None:
+        assert not accumulate
+        dx_out = torch.empty(r, k, dtype=torch.float32, device=dev)
+    nbytes = lib.raw("dc_gemm_tn_workspace_bytes")(r, n, k)
+    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
+    batch = getattr(_TN, "batch", None)
+    _hint_planes(w, True)
+    if batch is not None:
+        slabs = ctypes.c_int32(0)
+        lib.call("dc_linear_backward_both_slabs", dh, dh.stride(0), x, x.stride(0), w, w.stride(0), r, n, k, dx_out,
+                 dx_out.stride(0), int(accumulate), 0, ws, ws.numel() * 4, ctypes.byref(slabs))
+        batch.add(ws, slabs.value, n, k, dw, k)
+    else:
+        lib.call("dc_linear_backward_both", dh, dh.stride(0), x, x.stride(0), w, w.stride(0), r, n, k, dw, k, 0, dx_out,
+                 dx_out.stride(0), int(accumulate), 0, ws, ws.numel() * 4)
+    return dw, dx_out
+
+
 def linear_grads(dh, x, w, dx_out=None, accumulate=False, need_dx=True, need_dw=True):
     """The gradients of y = x w^T for the incoming dh [R, N]: -> (dW [N, K], dX [R, K]), None for one that is not needed
     (ctx.needs_input_grad of the caller); dX lands in `dx_out` (+= when accumulate) if given."""
     dh = _rowmajor(dh)
+    if need_dx and need_dw and _both_applies(dh, x, w, dx_out):
+        return _linear_grads_both(dh, _rowmajor(x), _rowmajor(w), dx_out, accumulate)
     dw = gemm_tn(dh, x if x.stride(1) == 1 else x.contiguous()) if need_dw else None
     return dw, (mm_nn(dh, w, out=dx_out, accumulate=accumulate) if need_dx else None)
 
@@ -974,6 +1011,21 @@ def bn_block_products(state, want_dinp=True, dinp_out=None, accumulate=False):
     nb2 = lib.raw("dc_gemm_tn_workspace_bytes")(r, c, k)
     ws2 = torch.empty((nb2 + 3) // 4, dtype=torch.float32, device=dev)
     batch = getattr(_TN, "batch", None)
+    if want_dinp:
+        # both products from one entry point: one launch where the library holds their pair of kernels (csrc/gemm.hip:
+        # gemm_dual_kernel; option 14 = 1: never), else the two launches of the separate calls below -- the same bits
+        dinp = dinp_out if dinp_out is not None else torch.empty(r, k, dtype=torch.float32, device=dev)
+        W = _rowmajor(W)
+        _hint_planes(W, True)
+        if batch is not None:
+            slabs = ctypes.c_int32(0)
+            lib.call("dc_linear_bn_backward_both_slabs", dy, lddy, h, c, coefs, slope, inp, inp.stride(0), W, W.stride(0), r, c, k,
+                     dinp, dinp.stride(0), int(accumulate), 0, ws2, ws2.numel() * 4, ctypes.byref(slabs))
+            batch.add(ws2, slabs.value, c, k, dW, k)
+        else:
+            lib.call("dc_linear_bn_backward_both", dy, lddy, h, c, coefs, slope, inp, inp.stride(0), W, W.stride(0), r, c, k, dW, k,
+                     0, dinp, dinp.stride(0), int(accumulate), 0, ws2, ws2.numel() * 4)
+        return dW, dg, db, dinp
     if batch is not None:
         slabs = ctypes.c_int32(0)
         lib.call("dc_linear_bn_backward_weight_slabs", dy, lddy, h, c, coefs, slope, inp, inp.stride(0), r, c, k, ws2,
@@ -982,14 +1034,7 @@ def bn_block_products(state, want_dinp=True, dinp_out=None, accumulate=False):
     else:
         lib.call("dc_linear_bn_backward_weight", dy, lddy, h, c, coefs, slope, inp, inp.stride(0), r, c, k, dW, k, 0, ws2,
                  ws2.numel() * 4)
-    dinp = None
-    if want_dinp:
-        dinp = dinp_out if dinp_out is not None else torch.empty(r, k, dtype=torch.float32, device=dev)
-        W = _rowmajor(W)
-        _hint_planes(W, True)
-        lib.call("dc_linear_bn_backward_input", dy, lddy, h, c, coefs, slope, W, W.stride(0), r, c, k, dinp,
-                 dinp.stride(0), int(accumulate), 0)
-    return dW, dg, db, dinp
+    return dW, dg, db, None
 
 
 def bn_block_backward(dy, lddy, inp, h, coef, use_batch, gamma, slope, W, want_dinp=True, dinp_out=None,

@@ -53,7 +53,10 @@ const char* dc_last_error(void);
  * whole tile (lab);
  * 13: plain dense products over pre-split weight planes (forward, input gradient, the statistics epilogues, the paired launch):
  * 0 = the fp32 activation tiles reach LDS by 16-byte LDS-DMA into a ring of three buffers, 1 = through staging registers and
- * ds_write_b128 into two padded buffers (the earlier loop: fallback, A/B partner).  Same floats into the same MFMAs: same bits. */
+ * ds_write_b128 into two padded buffers (the earlier loop: fallback, A/B partner).  Same floats into the same MFMAs: same bits;
+ * 14: the two gradient products of a block through dc_linear_backward_both / dc_linear_bn_backward_both: 0 = ONE launch for the
+ * pairs of kernel instantiations in the library's table, 1 = always the two launches of the separate calls (fallback, A/B partner).
+ * Same workgroups on the same data: same bits. */
 int dc_set_option(int32_t key, int32_t value);
 
 /* Deferred finalisers (round 6): a column reduction is two launches (partials, finaliser).  Between dc_finalisers_begin() and
@@ -649,6 +652,30 @@ int dc_linear_bn_backward_weight(const float* dy, int64_t lddy, const float* h, 
 int dc_linear_bn_backward_weight_slabs(const float* dy, int64_t lddy, const float* h, int64_t ldh, const float* coefs,
                                        float slope, const float* X, int64_t ldx, int64_t R, int32_t N, int32_t K,
                                        void* workspace, size_t workspace_bytes, int32_t* slabs, void* stream);
+
+/* Both gradients of a block in ONE call: dW[N,K] (lddw) (+)= dh^T X and dX[R,K] (lddx) (+)= dh W for dh [R,N] = dY (plain form:
+ * what dc_gemm_tn(dY, X) and dc_linear_backward_input compute) or the BatchNorm-backward prologue of (dy, h, coefs) (what
+ * dc_linear_bn_backward_weight and dc_linear_bn_backward_input compute).  Each product picks its tile, load mode, multiply path and
+ * slab plan as in those calls (a plane hint of dc_gemm_next_b_planes goes to the input-gradient product); the two read the same dh
+ * and write disjoint outputs, so where the library holds their pair of kernel instantiations they run as one launch
+ * (gemm_dual_kernel: the weight-gradient workgroups first, the input-gradient workgroups fill the CUs behind them), otherwise --
+ * ragged shapes, the exact chain, weight gradients that run the plane-image kernel, option 14 = 1 -- as the two launches of the
+ * separate calls.  The same bits either way.  Workspace: dc_gemm_tn_workspace_bytes(R, N, K).  The _slabs forms leave the partial
+ * tiles [slabs][N][K] in the workspace for dc_gemm_tn_reduce_many (*slabs: a HOST int). */
+int dc_linear_backward_both(const float* dY, int64_t lddy, const float* X, int64_t ldx, const float* W, int64_t ldw, int64_t R,
+                            int32_t N, int32_t K, float* dW, int64_t lddw, int32_t accumulate_w, float* dX, int64_t lddx,
+                            int32_t accumulate_x, int32_t tile, void* workspace, size_t workspace_bytes, void* stream);
+int dc_linear_backward_both_slabs(const float* dY, int64_t lddy, const float* X, int64_t ldx, const float* W, int64_t ldw,
+                                  int64_t R, int32_t N, int32_t K, float* dX, int64_t lddx, int32_t accumulate_x, int32_t tile,
+                                  void* workspace, size_t workspace_bytes, int32_t* slabs, void* stream);
+int dc_linear_bn_backward_both(const float* dy, int64_t lddy, const float* h, int64_t ldh, const float* coefs, float slope,
+                               const float* X, int64_t ldx, const float* W, int64_t ldw, int64_t R, int32_t N, int32_t K,
+                               float* dW, int64_t lddw, int32_t accumulate_w, float* dX, int64_t lddx, int32_t accumulate_x,
+                               int32_t tile, void* workspace, size_t workspace_bytes, void* stream);
+int dc_linear_bn_backward_both_slabs(const float* dy, int64_t lddy, const float* h, int64_t ldh, const float* coefs, float slope,
+                                     const float* X, int64_t ldx, const float* W, int64_t ldw, int64_t R, int32_t N, int32_t K,
+                                     float* dX, int64_t lddx, int32_t accumulate_x, int32_t tile, void* workspace,
+                                     size_t workspace_bytes, int32_t* slabs, void* stream);
 
 /* ---- per-cloud term of the segmentation head's first Linear ----------------------------------------------------------------
  * deltaconv/models/deltanet_segmentation.py:59-66: x_max[batch] (+ the category vector) is concatenated in front of the point
