@@ -15,3 +15,4 @@ from .pool_vectors import *       # noqa: F401,F403
 from .resample import CloudPair, fps_levels, prefix_levels    # noqa: F401
 from .voxel import voxel_subsample                   # noqa: F401
 from .cluster import *            # noqa: F401,F403
+from .cluster_vectors import *    # noqa: F401,F403

@@ -975,6 +975,56 @@ int dc_cluster_mean3(const float* p, int64_t num_points, const int64_t* cptr, co
 int dc_cluster_majority(const int64_t* labels, int64_t num_points, const int64_t* cptr, const int64_t* members, int64_t num_cells,
                         int32_t num_classes, int64_t* out, void* stream);
 
+/* ---- pooling of tangent-vector features over the cells of a cluster vector (csrc/cluster_vectors.hip, cluster_vectors_math.h) ---- */
+/* geometry.cluster_rotation / ClusterPair.rotation: the per-POINT table of parallel transports between every point's frame and the
+ * frame of its cell (deltaconv/geometry/connection.py:6-47 as dcconn::transport), 16 bytes per point.
+ *   cluster     DEVICE int64 [num_points]; a value outside [0, num_cells) names no cell: four +0.0f
+ *   fine_*      DEVICE [num_points,3] contiguous fp32: normal, x-axis, y-axis of the points' frames
+ *   coarse_*    DEVICE [num_cells,3] contiguous fp32: those of the cells' frames
+ *   to_cell     1 ("down"): entry i = transport(target: cell frame (n, x, y), source: point frame (n, x)); fine_y is not read and may
+ *               be NULL.  0 ("up"): entry i = transport(target: point frame (n, x, y), source: cell frame (n, x)); coarse_y may be NULL
+ *   rmat        DEVICE [num_points,4] fp32, 16-byte aligned, row-major 2 x 2
+ * Sizes out of range, to_cell outside {0, 1}, a null or misaligned pointer: DC_ERR_ARG.  One thread per point, one launch. */
+int dc_cluster_rotation(const int64_t* cluster, int64_t num_points, int64_t num_cells, const float* fine_normal, const float* fine_x,
+                        const float* fine_y, const float* coarse_normal, const float* coarse_x, const float* coarse_y,
+                        int32_t to_cell, int32_t non_oriented, float* rmat, void* stream);
+/* geometry.cluster_pool_vectors_rows / ClusterPair.down_vectors: v [2 num_points, C] (rows 2i, 2i+1 = the coefficients at point i
+ * in ITS frame) reduced over the lists of dc_cluster_lists, every member first carried into the cell's frame by rmat (the "down"
+ * table), by the rules of csrc/cluster_vectors_math.h: members in ascending row order; sum (au + R00 v0) + R01 v1 from +0, mean the
+ * sum divided once by the count, max per channel the transported vector of the member of largest squared norm (the first member, a
+ * later one iff strictly larger); an empty cell gives zeros.
+ *   mode        0 max, 2 sum, 3 mean (1, min, has no vector analogue: DC_ERR_ARG)
+ *   out         DEVICE [2 num_cells, C] fp32, rows ldo apart: every row is written
+ *   arg         DEVICE int32 [num_cells, C], rows ldarg apart (max; may be NULL for sum / mean, which do not write it): the ROW i
+ *               every channel came from, -1 for an empty cell
+ * The checks of dc_cluster_pool, and a misaligned rmat: DC_ERR_ARG.  One thread per (cell, group of 4 channels), four members in
+ * flight, 16-byte loads where v, ldv and C allow; one launch, no atomics, no synchronisation. */
+int dc_cluster_pool_vectors(const float* v, int64_t ldv, int64_t num_points, int32_t C, const int64_t* cptr, const int64_t* members,
+                            int64_t num_cells, const float* rmat, int32_t mode, float* out, int64_t ldo, int32_t* arg, int64_t ldarg,
+                            void* stream);
+/* geometry.cluster_pool_vectors_rows_backward: the gradient of dc_cluster_pool_vectors w.r.t. v, a gather -- one thread per (point,
+ * group of 4 channels): with cl = cluster[i], R = rmat[i] (the same "down" table), g0 / g1 rows 2cl, 2cl+1 of g:
+ * du = R00 g0 + R10 g1, dw = R01 g0 + R11 g1 -- always (sum), with g0, g1 first divided by (float)(cptr[cl+1] - cptr[cl]) (mean), or
+ * where arg[cl,ch] == i and +0 elsewhere (max).  A point without a cell gets zeros; every row of dv is written.
+ *   g   DEVICE [2 num_cells, C] fp32, rows ldg apart;  cptr  read by the mean only;  arg, ldarg  what the forward wrote (max)
+ *   dv  DEVICE [2 num_points, C] fp32, rows ldv apart
+ * DC_ERR_ARG as above.  One launch, no atomics. */
+int dc_cluster_pool_vectors_backward(const float* g, int64_t ldg, int64_t num_cells, int32_t C, const int64_t* cluster,
+                                     int64_t num_points, const int64_t* cptr, const float* rmat, const int32_t* arg, int64_t ldarg,
+                                     int32_t mode, float* dv, int64_t ldv, void* stream);
+/* geometry.cluster_unpool_vectors_rows / ClusterPair.up_vectors: the cells' vectors x [2 num_cells, C] carried into every member's
+ * frame: out[2i] = R00 x0 + R01 x1, out[2i+1] = R10 x0 + R11 x1 with R = rmat[i] (the "up" table) and x0 / x1 rows 2cl, 2cl+1; zeros
+ * for a point without a cell.  out [2 num_points, C].  The same gather kernel through R as it stands.  One launch. */
+int dc_cluster_unpool_vectors(const float* x, int64_t ldx, int64_t num_cells, int32_t C, const int64_t* cluster, int64_t num_points,
+                              const float* rmat, float* out, int64_t ldo, void* stream);
+/* geometry.cluster_unpool_vectors_rows_backward: the gradient of dc_cluster_unpool_vectors w.r.t. x: per cell its members in
+ * ascending order from +0, R = rmat[i] (the "up" table), g0 / g1 rows 2i, 2i+1 of g [2 num_points, C]:
+ * du = (du + R00 g0) + R10 g1, dw = (dw + R01 g0) + R11 g1 -> dx [2 num_cells, C]; an empty cell gets zeros.  The walk kernel of
+ * dc_cluster_pool_vectors in sum mode through the transposed matrices: ordered, atomics-free.  One launch. */
+int dc_cluster_unpool_vectors_backward(const float* g, int64_t ldg, int64_t num_points, int32_t C, const int64_t* cptr,
+                                       const int64_t* members, int64_t num_cells, const float* rmat, float* dx, int64_t ldx,
+                                       void* stream);
+
 /* ---- surface sampling of a batch of triangle meshes (csrc/mesh.hip, csrc/mesh_math.h) ------------------------------------------ */
 /* Bytes of workspace dc_mesh_sample needs for meshes of F_total faces in all: the cdf, 8 bytes per face.  Reference:
  * deltaconv/transforms/sample_points.py:22-59 (the area vector of :29-32 is the only state between its stages). */
