@@ -93,8 +93,8 @@ def _ws(n, c):
 
 
 @functools.lru_cache(maxsize=None)
-def _device_graph(gname):
-    nbr, sizes = ER.graph(gname)
+def _device_graph(gname, graph=ER.graph):
+    nbr, sizes = graph(gname)
     n, k = nbr.shape
     nbr32 = nbr.to(torch.int32).to(DEV)
     ptr = torch.tensor([sum(sizes[:q]) for q in range(len(sizes) + 1)], dtype=torch.int32, device=DEV)
