@@ -23,6 +23,7 @@
 // does not help with: one far outlier stretches the box until the cloud falls into a few cells; the search then degrades towards
 // brute force on one thread per query -- correct, slow.
 #include "common.h"
+#include "knn_grid_build.h"
 #include "knn_grid_math.h"
 #include "list_scan.h"
 
@@ -290,6 +291,16 @@ int launch_cross(const float* query, const int64_t* qptr, const int64_t* rptr, i
 bool good_target(float t) { return t > 0.f && dcgrid::finite1(t); }
 
 }  // namespace
+
+// the build for fps_grid.hip (knn_grid_build.h): the same layout, the same five launches
+size_t dc_grid_build_bytes(long long num_points, long long num_clouds) { return layout(num_points, num_clouds).total; }
+long long dc_grid_build_capacity(size_t bytes, long long num_clouds) { return capacity(bytes, num_clouds); }
+int dc_grid_build(const char* name, const float* pos, const int64_t* ptr, int B, float target, void* workspace, long long cap,
+                  hipStream_t stream, DcGridBuild* out) {
+    const Work w = carve(workspace, cap, B);
+    *out = DcGridBuild{w.grids, w.lptr, w.pts, w.cap, w.rows};
+    return build(name, pos, ptr, B, target, w, stream);
+}
 
 DC_EXPORT size_t dc_knn_grid_workspace_bytes(int64_t num_points, int32_t num_clouds) {
     if (num_points < 0 || num_points > G_MAX_POINTS || num_clouds < 0) return 0;

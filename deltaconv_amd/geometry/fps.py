@@ -7,7 +7,8 @@ restatement in deltaconv_amd/csrc_host/fps.cpp behind a C ABI (include/deltaconv
 ``large=True`` clouds above that kernel's cap go through ``dc_geodesic_fps_large``, whose distance vector lives in global memory.
 
 ``fps`` is plain EUCLIDEAN farthest-point sampling for use inside a training step (csrc/fps_euclid.hip behind ``dc_fps_batch``):
-device offsets, one launch, nothing read on the host, capturable."""
+device offsets, one launch, nothing read on the host, capturable.  ``fps(method="grid")`` is the same sampler on a uniform cell
+grid (csrc/fps_grid.hip behind ``dc_fps_grid``) for clouds above that kernel's cap: the same picks, bit for bit."""
 import ctypes
 import os
 import warnings
@@ -53,6 +54,21 @@ FPS_MAX_POINTS = 16384        # DC_FPS_MAX_POINTS: a cloud's distance vector liv
 FPS_LARGE_MAX_POINTS = 262144 # DC_FPS_LARGE_MAX_POINTS: the distance vector in global memory, two frontier bit sets in LDS
 FPS_LARGE_POINTS_PER_LAUNCH = 1 << 20   # points of a group of large clouds: its workspace holds 140 bytes per point (140 MiB)
 FPS_EUCLID_MAX_POINTS = 16384 # DC_FPS_EUCLID_MAX_POINTS: a cloud's positions and minima live in the registers of one workgroup
+FPS_GRID_MAX_POINTS = 262144  # DC_FPS_GRID_MAX_POINTS: one key per 64 of a cloud's at most 2 n cells lives in the LDS of one workgroup
+# The sampler behind ``fps`` / ``fps_levels`` where the call names none: "brute" (dc_fps_batch, the register kernel) or "grid" (the
+# exact sampler over a uniform cell grid, csrc/fps_grid.hip: the same picks bit for bit, clouds up to FPS_GRID_MAX_POINTS).
+# DC_FPS=brute|grid; no policy picks by size.
+FPS_METHODS = ("brute", "grid")
+FPS_METHOD = [os.environ.get("DC_FPS", "") or "brute"]
+FPS_GRID_TARGET = 0.5         # mean points per cell where the call names none (csrc/fps_grid_math.h: DEFAULT_TARGET; README: measured)
+
+
+def fps_method(fn, method):
+    """The `method` argument of a sampler, None = the switch -> "brute" | "grid"."""
+    method = FPS_METHOD[0] if method is None else method
+    if method not in FPS_METHODS:
+        raise ValueError(f"{fn}: method = {method!r} (DC_FPS where the call names none), known: {', '.join(FPS_METHODS)}")
+    return method
 
 
 def coarse_sizes(ratio, largest, smallest):
@@ -95,7 +111,40 @@ def fps_launch(pos, ptr, optr, b, max_cloud, max_samples, total, start=None, out
     return out
 
 
-def fps(pos, ptr=None, batch=None, ratio=None, n_samples=None, start=None, ptr_info=None, out=None):
+def fps_grid_launch(pos, ptr, optr, b, max_cloud, max_samples, total, start=None, out=None, grid_target=None, stats=False):
+    """``dc_fps_grid`` on checked arguments, the workspace from torch's allocator -> rows int64 [total], or (rows, stats int64
+    [b,2]) with ``stats``."""
+    import torch
+    from .._lib import lib
+    fn = "fps"
+    if max_cloud > FPS_GRID_MAX_POINTS:
+        raise ValueError(f"{fn}: a cloud of {max_cloud} points; the grid sampler takes at most {FPS_GRID_MAX_POINTS} per cloud "
+                         "(FPS_GRID_MAX_POINTS: the keys of a cloud's cell blocks live in the LDS of one workgroup)")
+    target = float(FPS_GRID_TARGET if grid_target is None else grid_target)
+    if not (target > 0.0 and target < float("inf")):
+        raise ValueError(f"{fn}: grid_target = {grid_target!r} must be positive and finite")
+    if start is not None:
+        if not torch.is_tensor(start) or not start.is_cuda or start.dim() != 1 or start.shape[0] != b or \
+                start.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"{fn}: `start` must be a device int32 / int64 tensor of {b} ids local to their clouds")
+        start = start.to(torch.int32).contiguous()
+    if out is None:
+        out = torch.empty(total, dtype=torch.int64, device=pos.device)
+    elif not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.int64 or tuple(out.shape) != (total,) or \
+            not out.is_contiguous():
+        raise ValueError(f"{fn}: `out` must be a contiguous device int64 tensor of {total} rows")
+    st = torch.zeros((b, 2), dtype=torch.int64, device=pos.device) if stats else None
+    if b and total:
+        nbytes = int(lib.raw("dc_fps_grid_workspace_bytes")(int(pos.shape[0]), int(b)))
+        if nbytes == 0:
+            raise ValueError(f"{fn}: {int(pos.shape[0])} points in {b} clouds are out of range")
+        work = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.int64, device=pos.device)
+        lib.call("dc_fps_grid", pos, ptr, optr, b, int(max_cloud), int(max_samples), start, target, out, st, work, nbytes)
+    return (out, st) if stats else out
+
+
+def fps(pos, ptr=None, batch=None, ratio=None, n_samples=None, start=None, ptr_info=None, out=None, method=None, grid_target=None,
+        stats=False):
     """Euclidean farthest-point sampling of every cloud of a batch on the device, in ONE launch that reads nothing on the host
     (``torch_cluster.fps(pos, batch, ratio)``; csrc/fps_euclid.hip behind ``dc_fps_batch``).
 
@@ -113,11 +162,23 @@ def fps(pos, ptr=None, batch=None, ratio=None, n_samples=None, start=None, ptr_i
     ``pos[rows]`` samples to the identity prefix, which is what ``prefix_levels`` rests on.  Clouds above
     ``FPS_EUCLID_MAX_POINTS`` = 16 384 points, empty clouds where the host knows of them, host tensors and anything but float32
     [N,3] raise ``ValueError``; a ``pos`` that requires grad raises (nothing here is differentiable).  The call can be captured
-    by ``torch.cuda.graph`` when the sizes come from ``ptr_info`` and the batch is uniform or ``n_samples`` is given."""
+    by ``torch.cuda.graph`` when the sizes come from ``ptr_info`` and the batch is uniform or ``n_samples`` is given.
+
+    ``method``: "brute" (``dc_fps_batch``, the register kernel above) or "grid" (``dc_fps_grid``, csrc/fps_grid.hip: the SAME
+    picks bit for bit, found on a uniform cell grid -- a pick updates only the points near it; clouds up to
+    ``FPS_GRID_MAX_POINTS`` = 262 144 points; six launches and a workspace from torch's allocator, still nothing read on the
+    host), None = ``FPS_METHOD[0]`` (``DC_FPS``, default "brute").  ``grid_target``: the grid's mean points per cell (None =
+    ``FPS_GRID_TARGET``); it cannot change a pick, and with "brute" it raises.  ``stats=True`` (grid only) adds a third result,
+    int64 [B,2]: per cloud the point updates evaluated and the cells visited, summed over its picks."""
     import torch
     from . import _cross
     from .graph import _min_cloud, _ptr_from_batch
     fn = "fps"
+    method = fps_method(fn, method)
+    if method != "grid" and grid_target is not None:
+        raise ValueError(f"{fn}: grid_target sizes the cells of method='grid'; it cannot be combined with method='brute'")
+    if method != "grid" and stats:
+        raise ValueError(f"{fn}: stats are the grid sampler's (method='grid')")
     if not torch.is_tensor(pos) or not pos.is_cuda:
         raise ValueError(f"{fn}: `pos` must be a tensor on a HIP device (there is no CPU path)")
     if pos.dim() != 2 or pos.shape[1] != 3 or pos.dtype != torch.float32:
@@ -155,9 +216,12 @@ def fps(pos, ptr=None, batch=None, ratio=None, n_samples=None, start=None, ptr_i
         raise ValueError(f"{fn}: {b} clouds need {b + 1} offsets, got {ptr.numel()}")
     if b and mn < 1:
         raise ValueError(f"{fn}: empty cloud")
-    if b and mx > FPS_EUCLID_MAX_POINTS:
+    if b and method == "brute" and mx > FPS_EUCLID_MAX_POINTS:
         raise ValueError(f"{fn}: a cloud of {mx} points; the sampler takes at most {FPS_EUCLID_MAX_POINTS} per cloud "
                          "(FPS_EUCLID_MAX_POINTS: a cloud lives in the registers of one workgroup)")
+    if b and method == "grid" and mx > FPS_GRID_MAX_POINTS:
+        raise ValueError(f"{fn}: a cloud of {mx} points; the grid sampler takes at most {FPS_GRID_MAX_POINTS} per cloud "
+                         "(FPS_GRID_MAX_POINTS: the keys of a cloud's cell blocks live in the LDS of one workgroup)")
     if ratio is not None:
         optr, total = coarse_offsets(ptr, b, int(ratio), mx, mn)
         most = coarse_sizes(int(ratio), mx, mn)[0]
@@ -166,6 +230,9 @@ def fps(pos, ptr=None, batch=None, ratio=None, n_samples=None, start=None, ptr_i
         if b and mn < most:
             raise ValueError(f"{fn}: n_samples = {most}, but a cloud has only {mn} points")
         optr, total = torch.arange(b + 1, dtype=torch.int64, device=dev) * most, b * most
+    if method == "grid":
+        got = fps_grid_launch(pos.detach().contiguous(), ptr, optr, b, mx if b else 0, most, total, start, out, grid_target, stats)
+        return (got[0], optr, got[1]) if stats else (got, optr)
     return fps_launch(pos.detach().contiguous(), ptr, optr, b, mx if b else 0, most, total, start, out), optr
 
 

@@ -253,14 +253,18 @@ def prefix_levels(ptr_info, ratios):
     return levels
 
 
-def fps_levels(pos, ptr_info, ratios, start=None):
+def fps_levels(pos, ptr_info, ratios, start=None, method=None, grid_target=None):
     """``prefix_levels`` for clouds whose rows are in ANY order: the same list of ``(rows, ptr, info)`` with identical ``ptr`` and
     ``info``, but level 1's ``rows`` are the picks of ONE Euclidean farthest-point sampling launch (``geometry.fps`` with
     ``ratios[0]``, from ``start`` or every cloud's row 0), in pick order, and the ``rows`` of every deeper level are the prefix of
     level 1's rows per cloud -- FPS is greedy, so those ARE the coarser samples from the same start.  On clouds already in that
     pick order the result equals ``prefix_levels``; with no ratios it is ``prefix_levels``.  ``pos``: DEVICE float32 [N,3], the
-    rows of level 0.  A uniform batch synchronises nothing and can be captured."""
-    from .fps import fps_launch
+    rows of level 0.  A uniform batch synchronises nothing and can be captured.  ``method`` / ``grid_target``: the sampler, as in
+    ``geometry.fps`` ("brute" | "grid", None = ``FPS_METHOD[0]``; the same rows either way, "grid" takes larger clouds)."""
+    from .fps import fps_grid_launch, fps_launch, fps_method
+    method = fps_method("fps_levels", method)
+    if method != "grid" and grid_target is not None:
+        raise ValueError("fps_levels: grid_target sizes the cells of method='grid'; it cannot be combined with method='brute'")
     levels = prefix_levels(ptr_info, ratios)
     if len(levels) == 1:
         return levels
@@ -270,8 +274,9 @@ def fps_levels(pos, ptr_info, ratios, start=None):
     if levels[0][2].min_cloud < 1:
         raise ValueError("fps_levels: empty cloud")
     prefix1, ptr1, info1 = levels[1]
-    picks = fps_launch(pos.detach().contiguous(), levels[0][1].contiguous(), ptr1.contiguous(), int(ptr_info[1]), levels[0][2][2],
-                       info1[2], int(prefix1.shape[0]), start)
+    launch = fps_launch if method == "brute" else (lambda *a: fps_grid_launch(*a, grid_target=grid_target))
+    picks = launch(pos.detach().contiguous(), levels[0][1].contiguous(), ptr1.contiguous(), int(ptr_info[1]), levels[0][2][2],
+                   info1[2], int(prefix1.shape[0]), start)
     # level 1's row of every prefix row: pick r of cloud b stands where the prefix hierarchy has row r of cloud b
     slot = torch.empty(pos.shape[0], dtype=torch.int64, device=pos.device)
     slot[prefix1] = torch.arange(prefix1.shape[0], dtype=torch.int64, device=pos.device)

@@ -322,6 +322,42 @@ class DeviceDataset:
         return DeviceDataset(take(self.pos), ptr, np.full(s, m, dtype=np.int64), take(self.norm), take(self.x), take(self.y_point),
                              self.y_cloud, self.category)
 
+    def fps_subsample(self, n_samples, start=None, seed=None, method=None):
+        """The Euclidean sibling of ``geodesic_subsample``: a new store whose clouds each hold the ``n_samples`` Euclidean
+        farthest points of this one's (``geometry.fps``, one call for the whole store), rows in PICK order -- so ``prefix_levels``
+        on the new store is a farthest-point hierarchy.  ``start``: the first pick of every cloud (host sequence of ids local to
+        the cloud); otherwise drawn per cloud from ``(seed, dataset index)`` (``geometry.fps.fps_starts``; ``seed=None``: at
+        random).  ``method``: the sampler, as in ``geometry.fps`` ("brute": clouds up to 16 384 points; "grid": up to 262 144;
+        None: its switch) -- the same rows either way.  ``pos``, ``norm``, ``x`` and per-point ``y`` are gathered by the picks;
+        ``source_rows`` (int64 [S * n_samples]: the picked rows of THIS store) is set as ``voxel_subsample`` sets it, so
+        ``Propagator(sub, parent)`` is the way back.  A cloud of fewer than ``n_samples`` points raises ``ValueError`` naming it:
+        there is no tiling."""
+        from .geometry.fps import fps, fps_starts
+        from .geometry.graph import PtrInfo
+        m, s, dev, sizes = int(n_samples), len(self), self.device, self.sizes
+        if m < 1:
+            raise ValueError("fps_subsample: n_samples >= 1")
+        if s and sizes.min() < m:
+            i = int(np.argmin(sizes))
+            raise ValueError(f"fps_subsample: cloud {i} has {int(sizes[i])} points, fewer than n_samples = {m}")
+        if start is None:
+            starts = fps_starts(sizes, seed)
+        else:
+            starts = np.asarray(start, dtype=np.int64).reshape(-1)
+            if starts.shape != sizes.shape or (starts < 0).any() or (starts >= sizes).any():
+                raise ValueError("fps_subsample: `start` must hold one point of every cloud (ids local to the cloud)")
+        ptr = torch.arange(s + 1, dtype=torch.int64, device=dev) * m
+        if s:
+            info = PtrInfo(self.ptr, s, int(sizes.max()), int(sizes.min()))
+            rows, _ = fps(self.pos, ptr_info=info, n_samples=m, start=torch.from_numpy(starts.astype(np.int32)).to(dev), method=method)
+        else:
+            rows = torch.empty(0, dtype=torch.int64, device=dev)
+        take = lambda t: None if t is None else t[rows].contiguous()
+        sub = DeviceDataset(take(self.pos), ptr, np.full(s, m, dtype=np.int64), take(self.norm), take(self.x), take(self.y_point),
+                            self.y_cloud, self.category)
+        sub.source_rows = rows
+        return sub
+
     def voxel_subsample(self, size, origin=None, pick="centre", reduce=None, num_classes=None):
         """A new store that keeps of every cloud one point per occupied grid cell of edge ``size`` (``geometry.voxel_subsample``:
         the member nearest the cell centre, or with ``pick="first"`` the first one; ``origin=None``: every cloud's grid starts at

@@ -14,6 +14,7 @@ import torch
 
 from .deltanet_base import _ptr_info
 from .deltanet_segmentation import DeltaNetSegmentation
+from ..geometry.fps import FPS_METHODS
 from ..geometry.graph import Graph, _min_cloud
 from ..geometry.grad_div_mls import build_grad_div, build_tangent_basis, estimate_basis
 from ..geometry.resample import CloudPair, fps_levels, prefix_levels
@@ -29,11 +30,13 @@ class DeltaNetMultiscaleBase(torch.nn.Module):
     cloud's first ``ceil(n / ratios[l])`` rows.  ``forward(data)`` -> the list of level-0 scalar features: every output of the
     level-0 encoder, then the output of the level-0 decoder.  ``sampling``: ``"prefix"`` (the default) takes the rows as they
     stand -- a farthest-point hierarchy when they are in FPS pick order; ``"fps"`` runs one Euclidean farthest-point sampling
-    launch per forward pass (``geometry.fps_levels``) and is that hierarchy whatever the order of the rows."""
+    launch per forward pass (``geometry.fps_levels``) and is that hierarchy whatever the order of the rows.  ``fps_method``: the
+    sampler of ``sampling="fps"``, "brute" | "grid" as in ``geometry.fps`` (None: its switch, ``DC_FPS``); the same hierarchy
+    either way, "grid" takes clouds above 16 384 points."""
 
     def __init__(self, in_channels, enc_channels=((64, 64), (128,), (256,)), dec_channels=(128, 128), ratios=(4, 4), mlp_depth=1,
                  num_neighbors=20, k_down=16, k_up=3, grad_regularizer=0.001, grad_kernel_width=1, vector_pool="max",
-                 centralize_first=True, sampling="prefix"):
+                 centralize_first=True, sampling="prefix", fps_method=None):
         super().__init__()
         enc_channels = [list(c) for c in enc_channels]
         levels = len(enc_channels)
@@ -46,7 +49,9 @@ class DeltaNetMultiscaleBase(torch.nn.Module):
             raise ValueError(f"DeltaNetMultiscaleBase: vector_pool must be one of {_VECTOR_POOLS}, got {vector_pool!r}")
         if sampling not in _SAMPLINGS:
             raise ValueError(f"DeltaNetMultiscaleBase: sampling must be one of {_SAMPLINGS}, got {sampling!r}")
-        self.sampling = sampling
+        if fps_method is not None and fps_method not in FPS_METHODS:
+            raise ValueError(f"DeltaNetMultiscaleBase: fps_method must be None or one of {FPS_METHODS}, got {fps_method!r}")
+        self.sampling, self.fps_method = sampling, fps_method
         self.k, self.k_down, self.k_up = int(num_neighbors), int(k_down), int(k_up)
         self.ratios = [int(r) for r in ratios]
         self.grad_regularizer, self.grad_kernel_width, self.vector_pool = grad_regularizer, grad_kernel_width, vector_pool
@@ -88,7 +93,8 @@ class DeltaNetMultiscaleBase(torch.nn.Module):
         else:
             frames = tuple(estimate_basis(pos, Graph.knn(pos, 10, ptr_info=info), orientation=pos))
         levels = []
-        for rows, ptr, linfo in (fps_levels(pos, info, self.ratios) if self.sampling == "fps" else prefix_levels(info, self.ratios)):
+        for rows, ptr, linfo in (fps_levels(pos, info, self.ratios, method=self.fps_method) if self.sampling == "fps" else
+                                 prefix_levels(info, self.ratios)):
             p = pos if rows is None else pos[rows]
             fr = frames if rows is None else tuple(t[rows] for t in frames)
             graph = Graph.knn(p, self.k, ptr_info=linfo)
@@ -135,8 +141,8 @@ class DeltaNetMultiscaleSegmentation(DeltaNetSegmentation):
 
     def __init__(self, in_channels, num_classes, enc_channels=((64, 64), (128,), (256,)), dec_channels=(128, 128), ratios=(4, 4),
                  mlp_depth=1, num_neighbors=20, k_down=16, k_up=3, grad_regularizer=0.001, grad_kernel_width=1, vector_pool="max",
-                 centralize_first=True, embedding_size=1024, categorical_vector=False, sampling="prefix"):
+                 centralize_first=True, embedding_size=1024, categorical_vector=False, sampling="prefix", fps_method=None):
         super().__init__(in_channels, num_classes, embedding_size=embedding_size, categorical_vector=categorical_vector,
                          backbone=DeltaNetMultiscaleBase(in_channels, enc_channels, dec_channels, ratios, mlp_depth, num_neighbors,
                                                          k_down, k_up, grad_regularizer, grad_kernel_width, vector_pool,
-                                                         centralize_first, sampling=sampling))
+                                                         centralize_first, sampling=sampling, fps_method=fps_method))

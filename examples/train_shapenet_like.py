@@ -34,7 +34,8 @@ def shapenet_model(args, num_classes):
         return DeltaNetMultiscaleSegmentation(in_channels=3, num_classes=num_classes, mlp_depth=2, embedding_size=1024,
                                               num_neighbors=args.k, grad_regularizer=args.grad_regularizer,
                                               grad_kernel_width=args.grad_kernel, categorical_vector=True,
-                                              sampling=getattr(args, "sampling", "prefix"))
+                                              sampling=getattr(args, "sampling", "prefix"),
+                                              fps_method=getattr(args, "fps_method", None))
     return DeltaNetSegmentation(in_channels=3, num_classes=num_classes, conv_channels=[64, 128, 256], mlp_depth=2,
                                 embedding_size=1024, num_neighbors=args.k, grad_regularizer=args.grad_regularizer,
                                 grad_kernel_width=args.grad_kernel, categorical_vector=True)
@@ -132,6 +133,9 @@ def main(argv=None):
     ap.add_argument("--sampling", choices=("prefix", "fps"), default="prefix",
                     help="with --multiscale: prefix = the coarser levels are the first rows of every cloud (rows in FPS pick order); "
                          "fps = Euclidean farthest-point sampling inside the step (rows in any order)")
+    ap.add_argument("--fps-method", choices=("brute", "grid"), default=None,
+                    help="with --sampling fps: brute = the register kernel (clouds up to 16 384 points), grid = the exact sampler on a "
+                         "cell grid (the same picks, clouds up to 262 144 points); default: the DC_FPS switch")
     ap.add_argument("--device-loader", action="store_true",
                     help="with --data: keep the prepared dataset on the GPU, build and augment every batch in one launch "
                          "(deltaconv_amd.DeviceLoader) instead of per-shape transforms + collate + upload on the host")

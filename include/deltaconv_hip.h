@@ -34,6 +34,7 @@ extern "C" {
 #define DC_FPS_MAX_POINTS (16384) /* points per cloud dc_geodesic_fps_batch takes: 8 bytes of LDS per point in one workgroup */
 #define DC_FPS_LARGE_MAX_POINTS (262144) /* points per cloud dc_geodesic_fps_large takes: two bit sets of n / 8 bytes of LDS */
 #define DC_FPS_EUCLID_MAX_POINTS (16384) /* points per cloud dc_fps_batch takes: 16 points per thread of a 1024-thread workgroup, in registers */
+#define DC_FPS_GRID_MAX_POINTS (262144) /* points per cloud dc_fps_grid takes: one key per 64 of its at most 2 n cells in the LDS of one workgroup (64 KiB) */
 
 int32_t dc_version(void);
 const char* dc_last_error(void);
@@ -879,6 +880,34 @@ int dc_geodesic_fps_large(const void* pos, int32_t pos_is_f64, const int64_t* pt
  * captured call replays on positions written in place.  Stream-ordered. */
 int dc_fps_batch(const float* pos, const int64_t* ptr, const int64_t* optr, int32_t B, int32_t max_cloud, int32_t max_samples,
                  const int32_t* start, int64_t* rows, void* stream);
+
+/* ---- exact Euclidean farthest-point sampling on a cell grid, for large clouds (csrc/fps_grid.hip, csrc/fps_grid_math.h) ---------- */
+/* The workspace of one dc_fps_grid call: a function of the sizes alone, linear -- the grid build of dc_knn_grid
+ * (dc_knn_grid_workspace_bytes: about 48 bytes a point), 4 bytes of md a point and one 8-byte key for each of the
+ * 2 * num_points + num_clouds cells: about 68 bytes a point.
+ *   num_points  HOST: all points of the call, ptr[B] - ptr[0]
+ * 0: a negative size or more than 2^31 - 1 points. */
+size_t dc_fps_grid_workspace_bytes(int64_t num_points, int32_t num_clouds);
+/* dc_fps_batch for clouds of up to DC_FPS_GRID_MAX_POINTS = 262 144 points: the SAME picks, bit for bit, found on a uniform cell
+ * grid.  A pick updates only the points of the cells within Chebyshev distance R of its own, R the smallest radius whose bound
+ * (csrc/knn_grid_math.h: bound2) reaches the md the pick held when it was selected; no other point could change.  The rule, its
+ * proof and a serial reference: csrc/fps_grid_math.h.  pos, ptr, optr, max_samples, start and rows are dc_fps_batch's.
+ *   max_cloud  HOST: >= the largest cloud, <= DC_FPS_GRID_MAX_POINTS; it sizes the LDS table of the launch.  A cloud LARGER than
+ *              max_cloud claims, or one that does not lie inside the workspace's capacity, is not sampled: every one of its rows
+ *              gets -1 and its stats are 0 (nothing is read or written out of bounds)
+ *   target     HOST: the wanted mean number of points per cell (csrc/knn_grid_math.h: make_grid); any positive finite value
+ *              gives the same picks, it only moves the time and the stats
+ *   stats      DEVICE [B,2] int64 or NULL: per cloud the number of point updates evaluated, summed over its picks (the population
+ *              of every pick's box), and the number of cells in those boxes -- functions of the inputs and the target alone
+ *   workspace  DEVICE, 16-byte aligned, workspace_bytes >= dc_fps_grid_workspace_bytes(all points of the call, B)
+ * One workgroup per cloud; nothing is handed between workgroups.  A null pointer (pos, ptr, optr, rows, workspace), B < 0,
+ * max_samples < 0, max_cloud outside 0 .. DC_FPS_GRID_MAX_POINTS, a target that is not positive and finite, a misaligned or too
+ * small workspace: DC_ERR_ARG with a message; B = 0 returns DC_OK.  Integer atomics in the grid build only, no floating-point
+ * atomics; six launches whose sizes depend on B, max_cloud and workspace_bytes alone, so the call can be captured and a captured
+ * call replays on positions written in place.  Stream-ordered. */
+int dc_fps_grid(const float* pos, const int64_t* ptr, const int64_t* optr, int32_t B, int32_t max_cloud, int32_t max_samples,
+                const int32_t* start, float target, int64_t* rows, int64_t* stats, void* workspace, size_t workspace_bytes,
+                void* stream);
 
 /* ---- voxel-grid subsampling of device-resident clouds (csrc/voxel.hip, csrc/voxel_math.h) --------------------------------------- */
 /* The workspace of one dc_voxel_subsample call: a function of the sizes alone, linear -- 2 * num_points + num_clouds table slots of
